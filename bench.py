@@ -10,7 +10,20 @@ items, 36 objects, bert-base (12 x 768, 12 heads, FFN 3072), Adamax - every rank
 averaged over ranks with RCCL.  A "step" is one such pass over one synthetic batch whose tensors and index vectors are
 already resident in HBM when the timed region starts.  Weak scaling: B per GPU is fixed.
 
-Extra objects on the same line:
+A plain run sets up, warms up, times the --steps steps, writes the last timed step's outputs if --dump-outputs is given, and prints the
+line; "step_ms" (the spread of the timed steps) and "peak_hbm_gb" come from the timed region itself.  Every other figure takes work of
+its own and is measured only with --full:
+  python bench.py --gpus 1 --steps 10 --warmup 3 --full
+  python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs DIR
+
+--dump-outputs DIR: what the timed path computed in its LAST timed step (rank 0), as DIR/<name>.npy (float32; float64 for the loss),
+written right after the timed region (before anything --full adds): training - "loss", the answer "scores" of the step's forward and every
+trainable parameter after the step's update ("param.<name>"); --mode fwd - "scores"; --mode bert512 - the encoder's layer outputs of
+every part ("encoder_layers.part<i>", real token rows only).  Inputs are seeded, so two builds run with the same arguments can be
+compared output for output.  An array of more than 2^20 values is written as a fixed, seeded sample of its flattened values (the same
+positions in every run), so that the files stay under 64 MB in all.
+
+Extra objects on the same line (--full only):
   roofline     - the dominant kernel (the encoder's 768x768 / 768x3072 projections: gemm_16c_nt_256p8 in the default precision,
                  gemm_16_nt_256p8 in the plain 16-bit modes): ALGORITHMIC FLOPs (2 * real_tokens * N * K per launch, counted once -
                  the fp8 correction product of the default mode is overhead, not credit) / its HIP-event time measured live on
@@ -84,6 +97,12 @@ def parse():
     ap.add_argument("--launch-check", action="store_true",
                     help="plumbing check of the --gpus N self-launch: rendezvous (gloo on the CPU when there is no GPU), count the ranks "
                          "with an all-reduce, print {launch_check, ranks_seen} on rank 0 and exit - no product code runs")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure: parity against the reference's golden scores, the "
+                         "roofline and timeline passes, the (64, 512) encoder forward, the CPU baseline (train / fwd); the one-pass "
+                         "schedule and the GEMM share (--mode bert512).  The --no-* options still skip their part")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (see the module docstring)")
     return ap.parse_args()
 
 
@@ -98,6 +117,35 @@ def note(msg):
     """progress on stderr (the JSON line on stdout stays alone)"""
     if int(os.environ.get("RANK", "0")) == 0:
         print("[bench %7.1fs] %s" % (time.perf_counter() - _T0, msg), file=sys.stderr, flush=True)
+
+
+DUMP_SAMPLE = 1 << 20           # --dump-outputs: values per array before it is sampled
+DUMP_BUDGET = 64 << 20          # --dump-outputs: bytes in all
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: write each (name, tensor or float) of ``arrays`` as out_dir/<name>.npy - tensors as float32, Python floats as
+    float64.  A tensor of more than DUMP_SAMPLE values is written as the values at a seeded sample of DUMP_SAMPLE flat positions (sorted;
+    the same positions for the same shape in every run); the sample shrinks further if the files would exceed DUMP_BUDGET."""
+    os.makedirs(out_dir, exist_ok=True)
+    cap = DUMP_SAMPLE
+    while sum(min(v.numel(), cap) * 4 for _, v in arrays if torch.is_tensor(v)) > DUMP_BUDGET:
+        cap //= 2
+    total = 0
+    for name, v in arrays:
+        if torch.is_tensor(v):
+            flat = v.detach().reshape(-1)
+            if flat.numel() > cap:
+                idx = np.sort(np.random.default_rng(1033).choice(flat.numel(), size=cap, replace=False))
+                flat = flat[torch.from_numpy(idx).to(flat.device)]
+                arr = flat.float().cpu().numpy()
+            else:
+                arr = v.detach().float().cpu().numpy()
+        else:
+            arr = np.array([float(v)], dtype=np.float64)
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+        total += arr.nbytes
+    note("outputs of the last timed step: %d arrays, %.1f MB in %s" % (len(arrays), total / 2 ** 20, out_dir))
 
 
 def build_trainer(opt, cfg, device, seed=1033, process_group=None):
@@ -175,14 +223,15 @@ def live_parity(tr, opt, batch, golden):
             "reference": "unmodified reference, fp32 CPU, same seeded batch and weights (tests/golden/sdnet_e2e_full.npz)"}
 
 
-def bert512_measure(a, device, lib, precision, batch=64, steps=None, warmup=None):
+def bert512_measure(a, device, lib, precision, batch=64, steps=None, warmup=None, full=True, dump=None):
     """North-star shape: BERT-base + fused attention FORWARD on input_ids (B, L) all valid (default (64, 512)).
     Achieved TFLOP/s on the algorithmic 169 869 312 + 36 864 L flop per token against the 2.5 PF MFMA peak.
     The batch runs as ``--parts`` independent groups of sequences on their own streams: at 32 768 rows the two N = 768 products
     have 384 tiles = 1.5 rounds of the 256 CUs, and a second stream's kernels fill the half-empty rounds (tools/bert512_split.py).
-    The one-pass schedule is timed too and reported beside it."""
+    ``full``: the one-pass schedule is timed too and reported beside it, and its GEMMs are timed in a pass of their own (dt1 / gemm_*
+    are None without it).  ``dump``: a directory for the layer outputs of the timed schedule's last step (dump_outputs)."""
     from ruart_amd import hip, synth
-    from ruart_amd.bert import BertEncoderWeights, PackedTokens, bert_encode, _Buffers
+    from ruart_amd.bert import BertEncoderWeights, PackedTokens, bert_encode, layer_outputs, _Buffers
     steps = steps or a.steps
     warmup = a.warmup if warmup is None else warmup
     cfg = synth.bert_config()
@@ -193,7 +242,7 @@ def bert512_measure(a, device, lib, precision, batch=64, steps=None, warmup=None
     if os.environ.get("RUART_TILE_ORDER"):              # experiments: GROUP_M of the encoder GEMM's tile walk
         hip.check(lib.ruart_gemm_set_tile_order(int(os.environ["RUART_TILE_ORDER"])), "set_tile_order")
     L = a.seq_len
-    ids = torch.randint(1000, cfg["vocab_size"], (batch, L))
+    ids = torch.randint(1000, cfg["vocab_size"], (batch, L), generator=torch.Generator().manual_seed(1033))
     flops = batch * L * (169869312 + 36864 * L)
 
     def schedule(P):
@@ -202,11 +251,13 @@ def bert512_measure(a, device, lib, precision, batch=64, steps=None, warmup=None
                               mfma_long=precision in ("fp16", "bf16")) for i in range(0, batch, per)]
         bufs = [_Buffers() for _ in parts]
         streams = [torch.cuda.Stream(device=device) for _ in parts] if P > 1 else [torch.cuda.current_stream()]
+        outs = [None] * len(parts)
 
         def step():
-            for p, b, s in zip(parts, bufs, streams):
+            for j, (p, b, s) in enumerate(zip(parts, bufs, streams)):
                 with torch.cuda.stream(s):
-                    bert_encode(W, p, b)
+                    outs[j] = bert_encode(W, p, b)
+        step.outputs = lambda: [("encoder_layers.part%d" % j, layer_outputs(o)[:, :p.T]) for j, (p, o) in enumerate(zip(parts, outs))]
         return step
 
     def timed(step):
@@ -219,34 +270,42 @@ def bert512_measure(a, device, lib, precision, batch=64, steps=None, warmup=None
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) / steps
 
-    one = schedule(1)
-    dt1 = timed(one)
-    dt = timed(schedule(a.parts)) if a.parts > 1 else dt1
-    hip.check(lib.ruart_prof_enable(1), "prof_enable")
-    for _ in range(steps):
-        one()
-    torch.cuda.synchronize()
-    ms, n, fl = ctypes.c_double(), ctypes.c_longlong(), ctypes.c_double()
-    hip.check(lib.ruart_prof_read(ctypes.byref(ms), ctypes.byref(n), ctypes.byref(fl)), "prof_read")
-    lib.ruart_prof_enable(0)
-    return {"flops": flops, "dt": dt, "dt1": dt1, "gemm_ms": ms.value, "gemm_n": n.value, "gemm_flops": fl.value, "steps": steps, "L": L}
+    one = schedule(1) if full or a.parts <= 1 else None
+    dt1 = timed(one) if one is not None else None
+    headline = schedule(a.parts) if a.parts > 1 else one
+    dt = timed(headline) if a.parts > 1 else dt1
+    if dump:
+        dump_outputs(dump, headline.outputs())
+    r = {"flops": flops, "dt": dt, "dt1": dt1 if full else None, "gemm_ms": None, "gemm_n": 0, "gemm_flops": None, "steps": steps, "L": L}
+    if full:
+        hip.check(lib.ruart_prof_enable(1), "prof_enable")
+        for _ in range(steps):
+            one()
+        torch.cuda.synchronize()
+        ms, n, fl = ctypes.c_double(), ctypes.c_longlong(), ctypes.c_double()
+        hip.check(lib.ruart_prof_read(ctypes.byref(ms), ctypes.byref(n), ctypes.byref(fl)), "prof_read")
+        lib.ruart_prof_enable(0)
+        r.update(gemm_ms=ms.value, gemm_n=n.value, gemm_flops=fl.value)
+    return r
 
 
 def bert512(a, device, lib, out_stream=sys.stdout):
     note("bert512: building weights")
-    r = bert512_measure(a, device, lib, a.precision, batch=a.batch)
+    r = bert512_measure(a, device, lib, a.precision, batch=a.batch, full=a.full, dump=a.dump_outputs)
     flops, dt, dt1, L = r["flops"], r["dt"], r["dt1"], r["L"]
+    one_pass = None
+    if dt1 is not None:
+        one_pass = {"ms_per_step": round(dt1 * 1e3, 3), "achieved": round(flops / dt1 / 1e12, 1),
+                    "frac": round(flops / dt1 / 1e12 / PEAK_TFLOPS, 4),
+                    "gemm_only_tflops": round(r["gemm_flops"] / (r["gemm_ms"] * 1e-3) / 1e12, 1) if r["gemm_n"] else None,
+                    "gemm_share": round(r["gemm_ms"] / r["steps"] / (dt1 * 1e3), 3) if r["gemm_n"] else None}
     out = {"metric": "BERT-base + attention forward, (B=%d, L=%d), achieved TFLOP/s" % (a.batch, L), "value": round(flops / dt / 1e12, 1),
            "unit": "TFLOP/s", "n_gpus": 1, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt * 1e3, 3),
            "higher_is_better": True, "dtype": DTYPE[a.precision], "data": "synthetic",
            "config": {"workload": "north-star shape: bert-base forward over %d x %d valid tokens" % (a.batch, L),
                       "schedule": "%d independent group(s) of sequences, one stream each" % a.parts},
            "roofline": {"bound": "mfma", "achieved": round(flops / dt / 1e12, 1), "peak": PEAK_TFLOPS, "unit": "TFLOP/s",
-                        "frac": round(flops / dt / 1e12 / PEAK_TFLOPS, 4), "traffic": None,
-                        "one_pass": {"ms_per_step": round(dt1 * 1e3, 3), "achieved": round(flops / dt1 / 1e12, 1),
-                                     "frac": round(flops / dt1 / 1e12 / PEAK_TFLOPS, 4),
-                                     "gemm_only_tflops": round(r["gemm_flops"] / (r["gemm_ms"] * 1e-3) / 1e12, 1) if r["gemm_n"] else None,
-                                     "gemm_share": round(r["gemm_ms"] / r["steps"] / (dt1 * 1e3), 3) if r["gemm_n"] else None}}}
+                        "frac": round(flops / dt / 1e12 / PEAK_TFLOPS, 4), "traffic": None, "one_pass": one_pass}}
     print(json.dumps(out), file=out_stream, flush=True)
 
 
@@ -464,7 +523,8 @@ def main():
     note("batches staged: %d real word pieces per batch" % real_tokens)
     parity = None
     golden = os.path.join(ROOT, "tests", "golden", "sdnet_e2e_full.npz")
-    want_parity = rank == 0 and not a.no_parity and not a.stress and not a.unlock_bert and a.batch == 64 and os.path.exists(golden)
+    want_parity = (a.full and rank == 0 and not a.no_parity and not a.stress and not a.unlock_bert and a.batch == 64
+                   and os.path.exists(golden))
     # The parity check runs AFTER the timed region, on a second trainer built from the same seeds (the weights the timed one started
     # from).  Round 5: run first, on the timed trainer, its no-grad forward left torch's caching allocator with a block layout the
     # training steps then reused - and the timed steps ran 0.7-1.0 ms slower for it (22.7 -> 23.5 ms on the same box, interleaved,
@@ -515,10 +575,10 @@ def main():
             nb = None if a.no_prefetch else (staged[i + 1] if host_batches is not None else batches[(i + 1) % len(batches)])
             if host_batches is not None and not a.no_prefetch:
                 # as SDNetTrainer.train does: the batch after next is shipped inside update(), where the host waits for the step anyway
-                tr.update(b, i, next_batch=nb, stage_next=lambda: fresh(i + 2))
+                loss = tr.update(b, i, next_batch=nb, stage_next=lambda: fresh(i + 2))
                 staged[i + 2] = tr.staged
-            else:
-                tr.update(b, i, next_batch=nb)
+                return loss
+            return tr.update(b, i, next_batch=nb)
         else:
             tr.network.eval()
             tr.network.drop_emb = False
@@ -568,22 +628,32 @@ def main():
             step(i)
             torch.cuda.synchronize()
             note("warmup step %d done" % i)
+    # --dump-outputs: the last timed step's forward hands its answer scores to this hook (registered for that step only)
+    last_scores, hook, loss = [], None, None
     sync()
     t0 = time.perf_counter()
     marks, enq = [], []
     with caller_stream():
         for i in range(a.steps):
             ts = time.perf_counter()
+            if a.dump_outputs and rank == 0 and i == a.steps - 1:
+                hook = tr.network.register_forward_hook(lambda m, args, out: last_scores.append(out[0]))
             # the step index runs on from the warm-up: timed step 0 consumes the encoder pass that the last warm-up step launched ahead,
             # so all K timed steps are the pipelined schedule (rounds 1-5 restarted at 0: with an odd warm-up the first timed step asked
             # for the batch that had NOT been encoded ahead and ran a 15-ms encoder pass inline, ~+0.2 ms on the 20-step mean)
-            step(a.warmup + i)
+            loss = step(a.warmup + i)
             marks.append(time.perf_counter())     # (host time at which step i's call returned: update() ends with the step's loss readback)
             enq.append((getattr(tr, "host_enqueued_at", ts) - ts) * 1e3)      # host time until the whole step was enqueued (train mode)
         if a.mode == "train":
             tr.flush_readback()               # the last step's loss and NaN flag are read (and asserted) inside the bracket too
     sync()
     dt = time.perf_counter() - t0
+    if hook is not None:
+        hook.remove()
+        outputs = [("scores", last_scores[-1])]
+        if a.mode == "train":
+            outputs = [("loss", float(loss))] + outputs + [("param." + n, p) for n, p in tr.network.named_parameters() if p.requires_grad]
+        dump_outputs(a.dump_outputs, outputs)
     # the spread of the timed steps, always on the line: a uniform slow run, a transient and a slow first step look different here
     per_step = [(b - a_) * 1e3 for a_, b in zip([t0] + marks[:-1], marks)]
     step_ms = _dist(per_step)
@@ -615,7 +685,7 @@ def main():
     #  * "timed": the schedule of the timed region (encoder of the next batch beside the trunk).  There a GEMM shares the CUs
     #    with the trunk's kernels, so its launch-to-finish time also contains the trunk's work (roofline.timed_region).
     roof = timeline = None
-    if not a.no_roofline and a.precision in GEMM_KERNEL:
+    if a.full and not a.no_roofline and a.precision in GEMM_KERNEL:
         def profiled_pass(prefetch, mode):
             """K more steps under the library's event recorder.  mode 1: a hipEvent pair around every encoder GEMM launch (the roofline
             figures; ~100 events per step, which stretch the pipelined step by 2-3 ms) plus the step-stream marks; mode 2: marks only -
@@ -731,7 +801,7 @@ def main():
         note("parity vs the reference's golden scores: %s" % parity)
 
     b512 = None
-    if rank == 0 and world == 1 and not a.no_bert512 and a.mode == "train" and not a.stress and not a.unlock_bert:
+    if a.full and rank == 0 and world == 1 and not a.no_bert512 and a.mode == "train" and not a.stress and not a.unlock_bert:
         note("north-star shape (64, 512), plain f16 ...")
         torch.cuda.empty_cache()
         r = bert512_measure(a, device, lib, "fp16", batch=64, steps=10, warmup=3)
@@ -761,7 +831,7 @@ def main():
                "step_ms": step_ms, "timeline_ms": timeline if roof is not None else None,
                "roofline": roof, "parity": parity, "bert512": b512,
                "peak_hbm_gb": round(torch.cuda.max_memory_allocated(device) / 2 ** 30, 2)}
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             note("cpu baseline (oracle) ...")
             out["cpu_baseline"] = cpu_baseline(opt, cfg, 1, runs=1) if a.stress else cpu_baseline(opt, cfg, a.cpu_samples)
         print(json.dumps(out), file=out_stream, flush=True)

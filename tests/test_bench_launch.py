@@ -83,11 +83,67 @@ def test_two_rank_bench_rehearsal_on_one_gpu():
     collective in its set-up - while rank 1 waits, one JSON line from rank 0.  The numbers mean nothing; the run must end."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     env["RUART_BENCH_REHEARSE_ONE_GPU"] = "1"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--no-cpu-baseline",
-                        "--no-bert512"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--full",
+                        "--no-cpu-baseline", "--no-bert512"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
     out = json.loads(lines[0])
     assert out["n_gpus"] == 2 and out["ranks_seen"] == 2 and out["config"]["global_batch"] == 128
     assert out["parity"]["holds"] and out["parity"]["max_abs_err_vs_reference"] < 1e-3
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_dump_outputs_writes_float_arrays_and_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs' writer: tensors as float32, a Python float as float64; an array above DUMP_SAMPLE values becomes the values at
+    the same seeded positions in every call; the sample shrinks until the files fit DUMP_BUDGET."""
+    import numpy as np
+    import torch
+    bench = _bench_module()
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 1000)
+    big = torch.arange(5000, dtype=torch.float64)
+    arrays = [("loss", 1.25), ("small", torch.arange(6, dtype=torch.float16).reshape(2, 3)), ("big", big)]
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    loss, small, sample = (np.load(tmp_path / "a" / (n + ".npy")) for n in ("loss", "small", "big"))
+    assert loss.dtype == np.float64 and loss.tolist() == [1.25]
+    assert small.dtype == np.float32 and small.shape == (2, 3) and small.ravel().tolist() == list(range(6))
+    assert sample.dtype == np.float32 and sample.shape == (1000,)
+    assert np.all(np.diff(sample) > 0) and set(sample.tolist()) <= set(range(5000))      # sorted positions of the array itself
+    assert np.array_equal(sample, np.load(tmp_path / "b" / "big.npy"))                   # the same positions every time
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 4 * (6 + 400))
+    bench.dump_outputs(str(tmp_path / "c"), arrays)
+    assert np.load(tmp_path / "c" / "big.npy").shape == (250,)
+    assert sum(os.path.getsize(tmp_path / "c" / (n + ".npy")) - 128 for n in ("small", "big")) <= 4 * (6 + 400)
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_and_dumped_outputs(tmp_path):
+    """A plain run (no --full) times exactly --steps steps, prints the headline fields and leaves every --full figure out;
+    --dump-outputs writes the last timed step's loss, answer scores and trained parameters, under 64 MB in all."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
+    out_dir = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+                        "--dump-outputs", str(out_dir)], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["warmup"] == 2 and out["unit"] == "samples/s" and out["higher_is_better"] is True
+    assert out["ms_per_step"] > 0 and abs(out["value"] - 64 * 1e3 / out["ms_per_step"]) < 0.01 * out["value"]
+    assert out["roofline"] is None and out["parity"] is None and out["bert512"] is None and "cpu_baseline" not in out
+    files = sorted(os.listdir(out_dir))
+    assert "loss.npy" in files and "scores.npy" in files and "param.alphaBERT.npy" in files
+    assert sum(os.path.getsize(out_dir / f) for f in files) <= 64 << 20
+    loss, scores = np.load(out_dir / "loss.npy"), np.load(out_dir / "scores.npy")
+    assert loss.dtype == np.float64 and loss.shape == (1,) and np.isfinite(loss).all()
+    assert scores.dtype == np.float32 and scores.shape[0] == 64 and np.isfinite(scores).all()
+    assert all(np.load(out_dir / f).dtype == np.float32 for f in files if f.startswith("param."))

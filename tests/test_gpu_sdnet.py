@@ -87,7 +87,7 @@ def test_sdnet_forward_backward_vs_reference(golden, precision, tol_p, tol_g):
     assert worst_elem[0] < 2 * tol_g, worst_elem
 
 
-def test_trainer_update_and_predict(golden):
+def test_trainer_update_and_predict(golden, tmp_path):
     from ruart_amd.trainer import SDNetTrainer
     z = golden
     opt = default_opt(vocab_size=1500, cuda=True, DROPOUT=0.0, dropout_emb=0.0)      # deterministic: same batch must improve
@@ -105,7 +105,7 @@ def test_trainer_update_and_predict(golden):
     loss, anls, acc, res, save_res = tr.predict(tr.ToCUDA(batch))
     assert len(res) == 4 and all("answer" in r for r in res)
     # checkpoint round trip with the reference's format
-    path = "/tmp/ruart_ckpt_test.pt"
+    path = str(tmp_path / "ruart_ckpt_test.pt")
     tr.save_for_predict(path)
     ck = torch.load(path, map_location="cpu")
     assert not any(k.startswith("Bert") for k in ck["state_dict"]["network"])
@@ -688,7 +688,7 @@ def test_unlocked_16bit_encoder_is_repeatable_and_falls_back(golden_dir):
 
 
 @pytest.mark.parametrize("train_gemm", ["x3", "16"])
-def test_unlocked_bert_trains_with_the_fused_optimizer(train_gemm):
+def test_unlocked_bert_trains_with_the_fused_optimizer(train_gemm, tmp_path):
     """The trainer path without LOCK_BERT: BERT's parameters sit in the (fused) Adamax, its own dropout is active in training
     (hidden 0.1 / attention 0.1, modeling.py:198-301) and off in evaluation, the loss on a fixed batch goes down, the
     checkpoint keeps the reference's habit of leaving ``Bert.*`` out.  "16": the 16-bit encoder (bert_train16.py), whose dropout
@@ -723,7 +723,7 @@ def test_unlocked_bert_trains_with_the_fused_optimizer(train_gemm):
     s1, _ = tr.network(batch[0], batch[1], batch[2])
     s2, _ = tr.network(batch[0], batch[1], batch[2])
     assert not torch.equal(s1, s2)                                       # training: BERT dropout on
-    path = "/tmp/ruart_ckpt_unlocked.pt"
+    path = str(tmp_path / "ruart_ckpt_unlocked.pt")
     tr.save_for_predict(path)
     assert not any(k.startswith("Bert") for k in torch.load(path, map_location="cpu")["state_dict"]["network"])
 

@@ -2,7 +2,7 @@
 # A/B of library variants in the pipelined step: tools/r04_ab.sh name1 name2 ...  (build/libruart_hip_<name>.so; "cur" = the product library)
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r04; mkdir -p $O; rm -f $O/ab_*.json
-B="python3 bench.py --no-cpu-baseline --no-bert512 --no-parity"
+B="python3 bench.py --full --no-cpu-baseline --no-bert512 --no-parity"
 for i in 1 2 3; do
   for v in "$@"; do
     if [ "$v" = cur ]; then $B > $O/ab_${v}_$i.json 2>/dev/null; else RUART_HIP_LIB=build/libruart_hip_$v.so $B > $O/ab_${v}_$i.json 2>/dev/null; fi

@@ -2,7 +2,7 @@
 # round 4, session 2: the step with NO trunk work (the encoder pass of the next batch, the optimizer, the host) and without pooling
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r04; mkdir -p $O; rm -f $O/abl2_*.json
-B="python3 bench.py --no-cpu-baseline --no-bert512 --no-parity"
+B="python3 bench.py --full --no-cpu-baseline --no-bert512 --no-parity"
 for i in 1 2; do
   for v in none trunk pool lstm,x3,attn lstm,x3,attn,pool; do
     RUART_DIAGNOSTICS=1 RUART_ABL_SKIP=$v $B > $O/abl2_${v//,/+}_$i.json 2> $O/abl2_${v//,/+}_$i.err || tail -3 $O/abl2_${v//,/+}_$i.err

@@ -2,7 +2,7 @@
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r04; mkdir -p $O
 python3 -m pytest tests/test_gpu_kernels.py tests/test_gpu_sdnet.py -x -q > $O/attn_tests.log 2>&1; echo "tests rc $?"; tail -3 $O/attn_tests.log
-B="python3 bench.py --no-cpu-baseline --no-bert512"
+B="python3 bench.py --full --no-cpu-baseline --no-bert512"
 for i in 1 2; do
   RUART_HIP_LIB=build/libruart_hip_oldx3.so $B > $O/at_step_old_$i.json 2>/dev/null; $B > $O/at_step_new_$i.json 2>/dev/null
 done

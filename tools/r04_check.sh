@@ -3,7 +3,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r04; mkdir -p $O
 python3 -m pytest tests -m gpu -x -q > $O/check_tests.log 2>&1; echo "tests rc $?"; tail -3 $O/check_tests.log
 python3 tools/x3_step_shapes.py > $O/x3_shapes_new2.log 2>&1; tail -1 $O/x3_shapes_new2.log
-B="python3 bench.py --no-cpu-baseline --no-bert512"
+B="python3 bench.py --full --no-cpu-baseline --no-bert512"
 for i in 1 2; do
   RUART_HIP_LIB=build/libruart_hip_oldx3.so $B > $O/ck_step_old_$i.json 2>/dev/null; $B > $O/ck_step_new_$i.json 2>/dev/null
 done

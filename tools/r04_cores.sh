@@ -2,7 +2,7 @@
 # round 4: does a GEMM that leaves registers free for co-resident trunk waves shorten the pipelined step? + op inventory with shapes
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r04; mkdir -p $O
-B="python3 bench.py --no-cpu-baseline --no-parity --no-bert512"
+B="python3 bench.py --full --no-cpu-baseline --no-parity --no-bert512"
 for i in 1 2; do
   $B > $O/cores_base_$i.json 2>/dev/null && RUART_HIP_LIB=build/libruart_hip_v224.so $B > $O/cores_v224_$i.json 2>/dev/null
 done

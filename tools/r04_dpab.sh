@@ -1,7 +1,7 @@
 #!/bin/bash
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r04; mkdir -p $O; rm -f $O/dpab_*.json
-B="python3 bench.py --no-cpu-baseline --no-bert512 --no-parity"
+B="python3 bench.py --full --no-cpu-baseline --no-bert512 --no-parity"
 for i in 1 2 3; do
   for cfg in "0 " "1 " "0 --force-dp" "1 --force-dp"; do
     set -- $cfg

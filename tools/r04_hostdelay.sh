@@ -2,7 +2,7 @@
 # round 4, session 2: is the host's enqueue time of the trunk forward on the step's critical path?  A busy-wait of N us at the start of the trunk
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r04; mkdir -p $O; rm -f $O/hd_*.json
-B="python3 bench.py --no-cpu-baseline --no-bert512 --no-parity"
+B="python3 bench.py --full --no-cpu-baseline --no-bert512 --no-parity"
 $B > /dev/null 2>&1
 for i in 1 2; do
   for d in 0 1000 2000 4000; do

@@ -2,7 +2,7 @@
 # round 4, session 2: the older trunk knobs again, now that the trunk runs at LOW priority (split-K fill target, one trunk stream)
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r04; mkdir -p $O; rm -f $O/kn_*.json
-B="python3 bench.py --no-cpu-baseline --no-bert512 --no-parity"
+B="python3 bench.py --full --no-cpu-baseline --no-bert512 --no-parity"
 $B > /dev/null 2>&1
 for i in 1 2; do
   for cfg in "448 160 1" "224 160 1" "128 80 1" "64 40 1" "448 160 0" "896 320 1"; do

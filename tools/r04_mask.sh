@@ -1,7 +1,7 @@
 #!/bin/bash
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r04; mkdir -p $O; rm -f $O/mask_*.json
-B="python3 bench.py --no-cpu-baseline --no-bert512 --no-parity"
+B="python3 bench.py --full --no-cpu-baseline --no-bert512 --no-parity"
 for i in 1 2; do
   for v in 240 0 252 248 232 224; do
     RUART_PREFETCH_CUS=$v $B > $O/mask_${v}_$i.json 2>/dev/null

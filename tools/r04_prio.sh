@@ -2,7 +2,7 @@
 # round 4, session 2: trunk streams at LOW priority (hipStreamCreateWithPriority 1) beside the CU-masked encoder stream
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r04; mkdir -p $O; rm -f $O/prio_*.json
-B="python3 bench.py --no-cpu-baseline --no-bert512"
+B="python3 bench.py --full --no-cpu-baseline --no-bert512"
 for i in 1 2 3; do
   for v in 0 1 -1; do
     RUART_TRUNK_PRIORITY=$v $B > $O/prio_${v}_$i.json 2> $O/prio_${v}_$i.err || tail -3 $O/prio_${v}_$i.err

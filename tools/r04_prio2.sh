@@ -2,7 +2,7 @@
 # round 4, session 2: encoder stream {masked 240, unmasked, unmasked + HIGH} x trunk {normal, LOW}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r04; mkdir -p $O; rm -f $O/p2_*.json
-B="python3 bench.py --no-cpu-baseline --no-bert512"
+B="python3 bench.py --full --no-cpu-baseline --no-bert512"
 for i in 1 2; do
   for enc in "240 0" "0 0" "0 -1" "248 0" "224 0"; do
     set -- $enc

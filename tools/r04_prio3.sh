@@ -2,7 +2,7 @@
 # round 4, session 2: mask size with the trunk at LOW priority (baseline: 240 CUs, trunk normal)
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r04; mkdir -p $O; rm -f $O/p3_*.json
-B="python3 bench.py --no-cpu-baseline --no-bert512 --no-parity"
+B="python3 bench.py --full --no-cpu-baseline --no-bert512 --no-parity"
 $B > /dev/null 2>&1     # warm the box
 for i in 1 2 3 4; do
   for cfg in "240 0" "240 1" "248 1" "252 1" "244 1" "232 1"; do

@@ -2,7 +2,7 @@
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r04; mkdir -p $O; rm -f $O/tail_*.json
 python3 -m pytest tests/test_gpu_kernels.py -x -q -k "tail" > $O/tail_ktests.log 2>&1; echo "kernel tests rc $?"; tail -4 $O/tail_ktests.log
-B="python3 bench.py --no-cpu-baseline"
+B="python3 bench.py --full --no-cpu-baseline"
 for i in 1 2 3; do
   RUART_TAIL_CUS=0 $B > $O/tail_off_$i.json 2>/dev/null; $B > $O/tail_on_$i.json 2>/dev/null
 done

@@ -5,7 +5,7 @@ O=gpurun_out/r04; mkdir -p $O
 python3 -m pytest tests/test_gpu_kernels.py -x -q -k "x3 or gemm or linear or mm" > $O/x3_tests.log 2>&1; echo "tests rc $?"; tail -3 $O/x3_tests.log
 RUART_HIP_LIB=build/libruart_hip_oldx3.so python3 tools/x3_step_shapes.py > $O/x3_shapes_old.log 2>&1; tail -1 $O/x3_shapes_old.log
 python3 tools/x3_step_shapes.py > $O/x3_shapes_new.log 2>&1; tail -1 $O/x3_shapes_new.log
-B="python3 bench.py --no-cpu-baseline --no-bert512"
+B="python3 bench.py --full --no-cpu-baseline --no-bert512"
 for i in 1 2; do
   RUART_HIP_LIB=build/libruart_hip_oldx3.so $B > $O/x3_step_old_$i.json 2>/dev/null; $B > $O/x3_step_new_$i.json 2>/dev/null
 done

@@ -6,7 +6,7 @@ ROUNDS=${ROUNDS:-3}
 for i in $(seq 1 $ROUNDS); do
   for cfg in "$@"; do
     IFS='|' read -r name envs args <<< "$cfg"
-    env $envs python3 bench.py --no-cpu-baseline --no-bert512 --steps ${STEPS:-60} $args > $O/${name}_$i.json 2> $O/${name}_$i.err || { echo "$name run $i failed"; tail -3 $O/${name}_$i.err; }
+    env $envs python3 bench.py --full --no-cpu-baseline --no-bert512 --steps ${STEPS:-60} $args > $O/${name}_$i.json 2> $O/${name}_$i.err || { echo "$name run $i failed"; tail -3 $O/${name}_$i.err; }
   done
 done
 python3 - "$@" <<'PY'

@@ -2,7 +2,7 @@
 # round 5, call 1: the new bench line (step_ms, timeline_ms) at trunk priority LOW (default) / NORMAL, interleaved; then the graph probe
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r05; mkdir -p $O
-B="python3 bench.py --no-cpu-baseline --no-bert512"
+B="python3 bench.py --full --no-cpu-baseline --no-bert512"
 for i in 1 2; do
   for v in 1 0; do
     RUART_TRUNK_PRIORITY=$v RUART_BENCH_STEP_TIMES=1 $B > $O/first_p${v}_$i.json 2> $O/first_p${v}_$i.err || tail -3 $O/first_p${v}_$i.err

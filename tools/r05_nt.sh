@@ -7,7 +7,7 @@ for v in nt0 "" ntln; do
   echo "== library [${v:-default}]"
   RUART_HIP_LIB=$L python3 tools/encoder_kernel_times.py 2>&1 | grep "encoder pass"
 done
-B="python3 bench.py --no-cpu-baseline --no-bert512"
+B="python3 bench.py --full --no-cpu-baseline --no-bert512"
 for i in 1 2 3; do
   for v in nt0 "" ntln; do
     L=""; [ -n "$v" ] && L="build/libruart_hip_$v.so"

@@ -7,7 +7,7 @@ import json,sys
 d=json.loads(open('$1').read().strip().splitlines()[-1])
 print('$2', d['ms_per_step'], {k:v for k,v in d['step_ms'].items() if k!='what'}, {k:v for k,v in (d['timeline_ms'] or {}).items() if k!='what'}, d['roofline'] and d['roofline']['avg_launch_us'])"; }
 timeout -k 10 400 python3 tools/graph_timing.py > $O/graph_timing.log 2>&1; grep "graph=" $O/graph_timing.log
-B="python3 bench.py --no-cpu-baseline --no-bert512 --no-parity"
+B="python3 bench.py --full --no-cpu-baseline --no-bert512 --no-parity"
 $B --steps 300 --no-roofline > $O/long300.json 2> $O/long300.err; python3 -c "
 import json
 d=json.loads(open('$O/long300.json').read().strip().splitlines()[-1]); print('300 steps', d['ms_per_step'], d['step_ms'])"

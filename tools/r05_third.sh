@@ -7,7 +7,7 @@ import json,sys
 d=json.loads(open('$1').read().strip().splitlines()[-1])
 t=d.get('timeline_ms') or {}
 print('%-44s %6.2f ms  median %6.2f  enq %5.2f | fwd_end %s bwd_end %s enc_end %s gemm %s/%s' % ('$2', d['ms_per_step'], d['step_ms']['median'], d['step_ms'].get('host_enqueue_median',0), t.get('trunk_forward_end'), t.get('trunk_backward_end'), t.get('encoder_last_gemm_end'), t.get('gemm_us_beside_trunk'), t.get('gemm_us_after_trunk')))"; }
-B="python3 bench.py --no-cpu-baseline --no-bert512 --no-parity"
+B="python3 bench.py --full --no-cpu-baseline --no-bert512 --no-parity"
 run() { name=$1; shift; env "$@" $B $EXTRA > $O/m_$name.json 2> $O/m_$name.err && show $O/m_$name.json "$name" || tail -3 $O/m_$name.err; }
 EXTRA="--graph-trunk 1"
 run g1_default RUART_X=0

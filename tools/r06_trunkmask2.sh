@@ -10,4 +10,4 @@ RUART_TRUNK_CUS=0 EVAL_BETWEEN=1 timeout -k 10 300 python3 tools/r05_two_session
 echo "== default, evaluation FIRST" | tee -a $L &&
 EVAL_FIRST=1 SESSIONS=1 timeout -k 10 300 python3 tools/r05_two_sessions.py 2>&1 | grep -v Warning | tee -a $L &&
 timeout -k 10 600 python3 -m pytest tests/test_gpu_streams.py -x -q 2>&1 | tail -3 | tee -a $L &&
-(cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $GRAFT_REPO_ROOT/$O/prof_mask -o mask -- python3 $GRAFT_REPO_ROOT/bench.py --steps 20 --warmup 5 --no-bert512 --no-cpu-baseline > $GRAFT_REPO_ROOT/$O/prof_mask_bench.json 2> $GRAFT_REPO_ROOT/$O/prof_mask_bench.err; echo "rocprof bench rc $?" | tee -a $GRAFT_REPO_ROOT/$L; tail -c 600 $GRAFT_REPO_ROOT/$O/prof_mask_bench.json)
+(ROOT=$PWD; cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $ROOT/$O/prof_mask -o mask -- python3 $ROOT/bench.py --full --steps 20 --warmup 5 --no-bert512 --no-cpu-baseline > $ROOT/$O/prof_mask_bench.json 2> $ROOT/$O/prof_mask_bench.err; echo "rocprof bench rc $?" | tee -a $ROOT/$L; tail -c 600 $ROOT/$O/prof_mask_bench.json)
