@@ -403,6 +403,23 @@ int ruart_whole_ln_fwd(const float* x, float* y, float* stats, float* ws, long l
 int ruart_whole_ln_bwd(const float* y, const float* grad_y, const float* stats, float* grad_x, float* ws, long long n,
                        void* stream);
 
+/* The same layer norm over the tensors of W data-parallel ranks taken together (the caller exchanges the partials between ranks).
+ * ruart_whole_ln_blocks(): P, the number of per-block partials one rank contributes per sum.
+ * ruart_whole_ln_partials: part[0..P) = block partials of sum(x); with x2 != NULL also part[P..2P) = those of sum(x * x2).
+ * The _global forms take part_all / part2_all = the partials of all W ranks, rank-major (W x P floats; W x 2P for the backward:
+ * per rank sum(grad_y) then sum(grad_y * y)), n = this rank's element count, n_total = the exact global one.  Every rank's P
+ * partials are reduced in the single-tensor kernels' order, then the W totals in rank order: with W = 1 the results are those of
+ * ruart_whole_ln_fwd / _bwd bit for bit.  Forward: partials(x) -> exchange -> var_global -> exchange -> apply_global;
+ * backward: partials(grad_y, y) -> exchange -> bwd_global. */
+int ruart_whole_ln_blocks(void);
+int ruart_whole_ln_partials(const float* x, const float* x2, float* part, long long n, void* stream);
+int ruart_whole_ln_var_global(const float* x, long long n, const float* part_all, int world, long long n_total, float* part2,
+                              void* stream);
+int ruart_whole_ln_apply_global(const float* x, float* y, long long n, float eps, const float* part_all, const float* part2_all,
+                                int world, long long n_total, float* stats, void* stream);
+int ruart_whole_ln_bwd_global(const float* y, const float* grad_y, const float* stats, float* grad_x, long long n,
+                              const float* part_all, int world, long long n_total, void* stream);
+
 /* Fused answer scorer: Models/Layers.py:352-432 (GetFinalScores with useES and no_answer, the two BilinearSeqAttn :435-468 and
  * get_single_score :421-432) for x (B, L, D) fp32 and per-sample vectors u1 (scores the OCR slots i >= ES), u2 (the first ES slots),
  * uh (the no-answer attention) (B, D) - the caller's three small projections of h0, variational-dropout masks of x folded in -,

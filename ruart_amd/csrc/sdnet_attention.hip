@@ -819,6 +819,92 @@ __global__ __launch_bounds__(256) void wln_bwd_kernel(const float* __restrict__ 
   }
 }
 
+// Cross-rank (data-parallel) forms.  The statistics are those of the W ranks' tensors taken together: `part` holds the per-block
+// partials of every rank, rank-major, `stride` floats apart; each rank's WLN_BLOCKS partials are re-reduced in grid_partial_total's
+// order, then the W rank totals are added in rank order.  Rank 0's total is the starting value, so with W = 1 every number is the
+// single-tensor kernels' own.  n is this rank's element count, n_total the exact global one (converted to float once, as above).
+__device__ __forceinline__ float wln_ranks_total(const float* part, int stride, int world, float* red) {
+  float t = grid_partial_total(part, red);
+  for (int r = 1; r < world; ++r) t += grid_partial_total(part + (long long)r * stride, red);
+  return t;
+}
+__global__ __launch_bounds__(256) void wln_var_global_kernel(const float* __restrict__ x, long long n, const float* __restrict__ part_all,
+                                                             int world, long long n_total, float* __restrict__ part2) {
+  __shared__ float red[4];
+  const float mean = wln_ranks_total(part_all, WLN_BLOCKS, world, red) / (float)n_total;
+  float q = 0.f;
+  if (wln_vec_ok(x, nullptr, nullptr, n)) {
+    const f32x4_t* x4 = reinterpret_cast<const f32x4_t*>(x);
+    const long long n4 = n >> 2;
+    WLN_FOR4(n4, f32x4_t a[4];
+             _Pragma("unroll") for (int u = 0; u < 4; ++u) a[u] = x4[ix_[u]];
+             _Pragma("unroll") for (int u = 0; u < 4; ++u) if (ok_[u]) {
+               const f32x4_t d = a[u] - mean;
+               q += (d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]);
+             })
+  } else {
+    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n; i += 256LL * WLN_BLOCKS) {
+      const float d = x[i] - mean;
+      q += d * d;
+    }
+  }
+  q = block_sum<4>(q, red);
+  if (threadIdx.x == 0) part2[blockIdx.x] = q;
+}
+__global__ __launch_bounds__(256) void wln_apply_global_kernel(const float* __restrict__ x, float* __restrict__ y, long long n, float eps,
+                                                               const float* __restrict__ part_all, const float* __restrict__ part2_all,
+                                                               int world, long long n_total, float* __restrict__ stats,
+                                                               int* __restrict__ nan_flag) {
+  __shared__ float red[4];
+  const float mean = wln_ranks_total(part_all, WLN_BLOCKS, world, red) / (float)n_total;
+  const float var = wln_ranks_total(part2_all, WLN_BLOCKS, world, red) / (float)n_total;
+  const float rstd = 1.0f / sqrtf(var + eps);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    stats[0] = mean;
+    stats[1] = rstd;
+  }
+  bool bad = false;
+  if (wln_vec_ok(x, y, nullptr, n)) {
+    const f32x4_t* x4 = reinterpret_cast<const f32x4_t*>(x);
+    f32x4_t* y4 = reinterpret_cast<f32x4_t*>(y);
+    const long long n4 = n >> 2;
+    WLN_FOR4(n4, f32x4_t a[4];
+             _Pragma("unroll") for (int u = 0; u < 4; ++u) a[u] = x4[ix_[u]];
+             _Pragma("unroll") for (int u = 0; u < 4; ++u) if (ok_[u]) {
+               const f32x4_t o = (a[u] - mean) * rstd;
+               y4[ix_[u]] = o;
+               bad |= !(o[0] == o[0]) || !(o[1] == o[1]) || !(o[2] == o[2]) || !(o[3] == o[3]);
+             })
+  } else {
+    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n; i += 256LL * WLN_BLOCKS) {
+      const float o = (x[i] - mean) * rstd;
+      y[i] = o;
+      bad |= !(o == o);
+    }
+  }
+  if (bad && nan_flag) atomicOr(nan_flag, 1);
+}
+// part_all: per rank 2 * WLN_BLOCKS floats, the sum-kernel partials of (sum gy, sum gy * y) as wln_sum_kernel(gy, y) writes them
+__global__ __launch_bounds__(256) void wln_bwd_global_kernel(const float* __restrict__ y, const float* __restrict__ gy,
+                                                             const float* __restrict__ stats, float* __restrict__ gx, long long n,
+                                                             const float* __restrict__ part_all, int world, long long n_total) {
+  __shared__ float red[4];
+  const float mg = wln_ranks_total(part_all, 2 * WLN_BLOCKS, world, red) / (float)n_total;
+  const float mgy = wln_ranks_total(part_all + WLN_BLOCKS, 2 * WLN_BLOCKS, world, red) / (float)n_total;
+  const float rstd = stats[1];
+  if (wln_vec_ok(y, gy, gx, n)) {
+    const f32x4_t* y4 = reinterpret_cast<const f32x4_t*>(y);
+    const f32x4_t* g4 = reinterpret_cast<const f32x4_t*>(gy);
+    f32x4_t* o4 = reinterpret_cast<f32x4_t*>(gx);
+    const long long n4 = n >> 2;
+    WLN_FOR4(n4, f32x4_t a[4], b[4];
+             _Pragma("unroll") for (int u = 0; u < 4; ++u) { a[u] = y4[ix_[u]]; b[u] = g4[ix_[u]]; }
+             _Pragma("unroll") for (int u = 0; u < 4; ++u) if (ok_[u]) o4[ix_[u]] = rstd * (b[u] - mg - a[u] * mgy);)
+  } else {
+    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n; i += 256LL * WLN_BLOCKS) gx[i] = rstd * (gy[i] - mg - y[i] * mgy);
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
 static bool g_attn_prefetch = !(getenv("RUART_ATTN_PREFETCH") && atoi(getenv("RUART_ATTN_PREFETCH")) == 0);
 template <typename K> static void attn_big_lds(K kern) { hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); }
@@ -1063,6 +1149,45 @@ extern "C" int ruart_whole_ln_bwd(const float* y, const float* grad_y, const flo
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(wln_sum_kernel, dim3(WLN_BLOCKS), dim3(256), 0, s, grad_y, y, n, ws);
   hipLaunchKernelGGL(wln_bwd_kernel, dim3(WLN_BLOCKS), dim3(256), 0, s, y, grad_y, stats, grad_x, n, ws);
+  RUART_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int ruart_whole_ln_blocks(void) { return WLN_BLOCKS; }
+
+extern "C" int ruart_whole_ln_partials(const float* x, const float* x2, float* part, long long n, void* stream) {
+  RUART_ENTRY();
+  if (n <= 0 || !x || !part) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(wln_sum_kernel, dim3(WLN_BLOCKS), dim3(256), 0, (hipStream_t)stream, x, x2, n, part);
+  RUART_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int ruart_whole_ln_var_global(const float* x, long long n, const float* part_all, int world, long long n_total, float* part2,
+                                         void* stream) {
+  RUART_ENTRY();
+  if (n <= 0 || world < 1 || n_total < n) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(wln_var_global_kernel, dim3(WLN_BLOCKS), dim3(256), 0, (hipStream_t)stream, x, n, part_all, world, n_total, part2);
+  RUART_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int ruart_whole_ln_apply_global(const float* x, float* y, long long n, float eps, const float* part_all, const float* part2_all,
+                                           int world, long long n_total, float* stats, void* stream) {
+  RUART_ENTRY();
+  if (n <= 0 || world < 1 || n_total < n) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(wln_apply_global_kernel, dim3(WLN_BLOCKS), dim3(256), 0, (hipStream_t)stream, x, y, n, eps, part_all, part2_all, world,
+                     n_total, stats, ruart_nan_flag_ptr);
+  RUART_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int ruart_whole_ln_bwd_global(const float* y, const float* grad_y, const float* stats, float* grad_x, long long n,
+                                         const float* part_all, int world, long long n_total, void* stream) {
+  RUART_ENTRY();
+  if (n <= 0 || world < 1 || n_total < n) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(wln_bwd_global_kernel, dim3(WLN_BLOCKS), dim3(256), 0, (hipStream_t)stream, y, grad_y, stats, grad_x, n, part_all,
+                     world, n_total);
   RUART_CHECK_LAUNCH();
   return 0;
 }

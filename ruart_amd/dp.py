@@ -3,7 +3,9 @@
 The reference has no distributed code at all; this is the new exchange step the north star
 asks for.  Design, for 8 MI355X on a fully connected xGMI mesh:
   * every rank runs the whole step on its own B-sample shard (samples are independent; the whole-tensor layer
-    norm couples samples only inside a replica, so the semantics are "N reference steps, gradients averaged");
+    norm couples samples only inside a replica, so the semantics are "N reference steps, gradients averaged" - unless
+    ``opt['dp_global_batch']`` takes its statistics over all ranks (make_ln_groups, ops.whole_layer_norm): then a W-rank step
+    at batch B is the single-process step at batch W * B);
   * only what must move moves: trainable, actually-used parameters.  The dead ``get_answer.rnn.*`` GRU (never gets a
     gradient, Models/Layers.py:395-397) is excluded.  The word-embedding rows >= tune_partial are re-pinned after every
     step (Models/SDNetTrainer.py:369-373) so their update never survives - but their gradients do enter the global clipping
@@ -61,6 +63,19 @@ def init_process_group(device, backend="nccl", **kw):
         kw.setdefault("pg_options", dist.ProcessGroupNCCL.Options(is_high_priority_stream=True))
         kw.setdefault("device_id", torch.device(device))
     return dist.init_process_group(backend, **kw)
+
+
+def make_ln_groups(group=None):
+    """opt['dp_global_batch']: the three process groups of the trunk's cross-rank layer norms (question, object, OCR branch; SDNet.
+    set_ln_groups), over the ranks of ``group`` (default: the world).  The branches run on three streams and a communicator runs its
+    collectives in issue order, so one shared group would make the object branch's first exchange wait behind the question branch's.
+    A collective call: every rank creates them once, in this order.  RCCL groups get the high-priority stream, as the gradient
+    exchange does (init_process_group): the exchanges sit on the branches' critical chains."""
+    ranks = None if group is None else dist.get_process_group_ranks(group)
+    kw = {}
+    if dist.get_backend(group) == "nccl":
+        kw["pg_options"] = dist.ProcessGroupNCCL.Options(is_high_priority_stream=True)
+    return tuple(dist.new_group(ranks=ranks, **kw) for _ in range(3))
 
 
 class GradSync:

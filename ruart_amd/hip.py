@@ -122,6 +122,11 @@ _SIGNATURES = {
     "ruart_attn_bwd_pscale": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "ruart_whole_ln_fwd": (_I, [_P, _P, _P, _P, _LL, _F, _P]),
     "ruart_whole_ln_bwd": (_I, [_P, _P, _P, _P, _P, _LL, _P]),
+    "ruart_whole_ln_blocks": (_I, []),
+    "ruart_whole_ln_partials": (_I, [_P, _P, _P, _LL, _P]),
+    "ruart_whole_ln_var_global": (_I, [_P, _LL, _P, _I, _LL, _P, _P]),
+    "ruart_whole_ln_apply_global": (_I, [_P, _P, _LL, _F, _P, _P, _I, _LL, _P, _P]),
+    "ruart_whole_ln_bwd_global": (_I, [_P, _P, _P, _P, _LL, _P, _I, _LL, _P]),
     "ruart_scorer_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "ruart_scorer_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "ruart_lstm_set_variant": (_I, [_I]),

@@ -131,7 +131,9 @@ class StackedBRNN(nn.Module):
             p += [r.weight_ih_l0_reverse, r.weight_hh_l0_reverse, r.bias_ih_l0_reverse, r.bias_hh_l0_reverse]
         return p
 
-    def forward(self, x, x_mask, return_list=False, x_additional=None, LN=None):
+    def forward(self, x, x_mask, return_list=False, x_additional=None, LN=None, ln_group=None):
+        """``ln_group``: the process group whose ranks' tensors the whole-tensor layer norms are taken over together
+        (opt['dp_global_batch'], ops.whole_layer_norm); None: this tensor alone."""
         hiddens = [x]
         for i in range(self.num_layers):
             rnn_input = hiddens[-1]
@@ -148,7 +150,7 @@ class StackedBRNN(nn.Module):
                     rnn_input = dropout(rnn_input, p=dropout_p, training=self.training)
                 out = lstm_layer_wide(rnn_input, *self.layer_params(i))
             if LN:
-                out = ops.whole_layer_norm(out)
+                out = ops.whole_layer_norm(out, group=ln_group)
             hiddens.append(out)
         output = torch.cat(hiddens[1:], 2) if self.concat_layers else hiddens[-1]
         return (output, hiddens[1:]) if return_list else output

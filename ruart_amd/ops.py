@@ -193,8 +193,73 @@ class _WholeLayerNorm(torch.autograd.Function):
         return gx, None
 
 
-def whole_layer_norm(x, eps=1e-5):
-    return _WholeLayerNorm.apply(x.contiguous(), eps)
+def _exchange_partials(group, width, fill, device):
+    """Gather every rank's ``width`` per-block partials of ``group``: each rank writes its own slot of a zeroed (W, width) buffer
+    (``fill(slot)``) and one all_reduce(SUM) adds zeros to everything else - an exact gather, on RCCL and gloo alike.  Returns the
+    (W * width) buffer, rank-major, and W."""
+    import torch.distributed as dist
+    world, rank = dist.get_world_size(group), dist.get_rank(group)
+    buf = torch.zeros(world * width, dtype=torch.float32, device=device)
+    fill(buf[rank * width:(rank + 1) * width])
+    dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=group)
+    return buf, world
+
+
+def whole_ln_global_fwd(x, eps, group):
+    """Forward of the cross-rank whole-tensor layer norm: (y, stats) with stats = (mean, rstd) of the tensors of all ranks of
+    ``group`` taken together.  Two exchanges of P = ruart_whole_ln_blocks() floats per rank.  Every rank's ``x`` has the same
+    number of elements (VQA_Sampler deals W equal shards), so the global count is W * x.numel(), exact."""
+    lib = hip.load()
+    hip.require_gpu(x, torch.float32)
+    nan_flag.ensure(x.device)
+    P, n, st = lib.ruart_whole_ln_blocks(), x.numel(), hip.stream_ptr()
+    part, world = _exchange_partials(group, P, lambda s: hip.check(lib.ruart_whole_ln_partials(
+        hip.ptr(x), None, hip.ptr(s), n, st), "ruart_whole_ln_partials"), x.device)
+    part2, _ = _exchange_partials(group, P, lambda s: hip.check(lib.ruart_whole_ln_var_global(
+        hip.ptr(x), n, hip.ptr(part), world, world * n, hip.ptr(s), st), "ruart_whole_ln_var_global"), x.device)
+    y = torch.empty_like(x)
+    stats = torch.empty(2, dtype=torch.float32, device=x.device)
+    hip.check(lib.ruart_whole_ln_apply_global(hip.ptr(x), hip.ptr(y), n, eps, hip.ptr(part), hip.ptr(part2), world, world * n,
+                                              hip.ptr(stats), st), "ruart_whole_ln_apply_global")
+    return y, stats
+
+
+def whole_ln_global_bwd(y, gy, stats, group):
+    """grad_x of the cross-rank whole-tensor layer norm: one exchange of 2 P floats per rank (sum gy, sum gy * y)."""
+    lib = hip.load()
+    gy = gy.contiguous()
+    P, n, st = lib.ruart_whole_ln_blocks(), y.numel(), hip.stream_ptr()
+    part, world = _exchange_partials(group, 2 * P, lambda s: hip.check(lib.ruart_whole_ln_partials(
+        hip.ptr(gy), hip.ptr(y), hip.ptr(s), n, st), "ruart_whole_ln_partials"), y.device)
+    gx = torch.empty_like(y)
+    hip.check(lib.ruart_whole_ln_bwd_global(hip.ptr(y), hip.ptr(gy), hip.ptr(stats), hip.ptr(gx), n, hip.ptr(part), world, world * n, st),
+              "ruart_whole_ln_bwd_global")
+    return gx
+
+
+class _GlobalWholeLayerNorm(torch.autograd.Function):
+    """_WholeLayerNorm over the tensors of every rank of a process group taken together (opt['dp_global_batch'], DESIGN.md section
+    6): the statistics of the global batch.  Forward and backward are collective calls on ``group``."""
+
+    @staticmethod
+    def forward(ctx, x, eps, group):
+        y, stats = whole_ln_global_fwd(x, eps, group)
+        ctx.group = group
+        ctx.save_for_backward(y, stats)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        y, stats = ctx.saved_tensors
+        return whole_ln_global_bwd(y, gy, stats, ctx.group), None, None
+
+
+def whole_layer_norm(x, eps=1e-5, group=None):
+    """F.layer_norm(x, x.size()).  ``group`` (a torch.distributed process group): normalise over the tensors of all its ranks as if
+    they were one, concatenated along the batch - every rank must call it, in the same order, with a tensor of the same size."""
+    if group is None:
+        return _WholeLayerNorm.apply(x.contiguous(), eps)
+    return _GlobalWholeLayerNorm.apply(x.contiguous(), eps, group)
 
 
 # ---------------------------------------------------------------------------------------------------------

@@ -44,3 +44,17 @@ class VQA_Sampler(Sampler):
             batch, pool = pool[:gb], pool[gb:]
             if b >= self.batch_st:
                 yield batch[self.rank::self.world]
+
+
+def merge_rank_shards(per_rank, batch_size):
+    """The inverse of the dealing above for an evaluation stream (every global batch full, the wrap-around fills the last one):
+    ``per_rank[r]`` = what rank r produced per sample, in its own order (its ``batch_size`` samples of global batch 0, then of
+    batch 1, ...).  Returns the list in the order of one process at batch ``W * batch_size``: global batch b, sample j is rank
+    j % W's entry b * batch_size + j // W."""
+    world = len(per_rank)
+    n = len(per_rank[0]) if per_rank else 0
+    if any(len(p) != n for p in per_rank) or n % batch_size:
+        raise ValueError("merge_rank_shards: every rank holds the same number of full batches of %d, got %s"
+                         % (batch_size, [len(p) for p in per_rank]))
+    gb = world * batch_size
+    return [per_rank[j % world][b * batch_size + j // world] for b in range(n // batch_size) for j in range(gb)]

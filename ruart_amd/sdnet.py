@@ -86,6 +86,7 @@ class _Trunk(nn.Module):
             if hasattr(net, name):
                 setattr(self, name, getattr(net, name))
         self._net_streams = net._side_streams       # eager mode shares the SDNet's two side streams (few HW queues)
+        self._net_ln_groups = net.ln_groups
         self._net_use_streams = net._use_streams
         self._bank = L.MaskBank()
 
@@ -112,19 +113,22 @@ class _Trunk(nn.Module):
             use_streams = self._net_use_streams()
             s_q, s_od = self._side_streams(dev) if use_streams else (main, main)
             _fork(main, (s_q, s_od), [q_input, q_raw, q_mask, x_od, od_mask])
+            # opt['dp_global_batch']: each branch's layer norms exchange their statistics over a process group of its own, so that
+            # no branch's collectives queue behind another's (SDNet.set_ln_groups); None: per-replica statistics
+            g_q, g_od, g_ocr = self._net_ln_groups()
 
             with torch.cuda.stream(s_q):                                        # ---- question branch (SDNet.py:339, 350)
-                _, q_rnn_layers = self.ques_rnn(q_input, q_mask, return_list=True, LN=True)
-                q_highlvl = self.high_lvl_ques_rnn(torch.cat(q_rnn_layers, 2), q_mask, LN=True)
+                _, q_rnn_layers = self.ques_rnn(q_input, q_mask, return_list=True, LN=True, ln_group=g_q)
+                q_highlvl = self.high_lvl_ques_rnn(torch.cat(q_rnn_layers, 2), q_mask, LN=True, ln_group=g_q)
                 q_rnn_layers = q_rnn_layers + [q_highlvl]
                 ev_q_layers = s_q.record_event() if use_streams else None
                 q_final = self.ques_self_attn(q_highlvl, q_highlvl, q_mask)    # SDNet.py:411-415
                 q_merged = self.ques_merger.merge(q_final, q_mask)
             q_long = [q_raw]
 
-            def context_branch(x, mask, helper=None):
+            def context_branch(x, mask, helper=None, ln_group=None):
                 """context_rnn, deep_attn, self-attention, high-level rnn for OCR tokens or objects"""
-                _, rnn_layers = self.context_rnn(x, mask, return_list=True, LN=True)
+                _, rnn_layers = self.context_rnn(x, mask, return_list=True, LN=True, ln_group=ln_group)
                 if ev_q_layers is not None:
                     torch.cuda.current_stream(dev).wait_event(ev_q_layers)
                     for t in q_rnn_layers:
@@ -132,13 +136,13 @@ class _Trunk(nn.Module):
                 h, pre = self.deep_attn([x], rnn_layers, q_long, q_rnn_layers, mask, q_mask, return_bef_rnn=True, helper=helper)
                 sa_in = torch.cat([h, pre, x], 2)
                 sa = self.highlvl_self_att(sa_in, sa_in, mask, x3=h)
-                return self.high_lvl_context_rnn(torch.cat([h, sa], 2), mask, LN=True)
+                return self.high_lvl_context_rnn(torch.cat([h, sa], 2), mask, LN=True, ln_group=ln_group)
 
             with torch.cuda.stream(s_od):                                       # ---- object branch
-                od_hl = context_branch(x_od, od_mask)
+                od_hl = context_branch(x_od, od_mask, ln_group=g_od)
             # ---- OCR branch (the longest chain) on the main stream; one of its three independent deep-attention levels borrows
             #      the question stream, which is idle by then
-            ocr_hl = context_branch(x_ocr, ocr_mask, helper=s_q if use_streams else None)
+            ocr_hl = context_branch(x_ocr, ocr_mask, helper=s_q if use_streams else None, ln_group=g_ocr)
             _join(main, (s_od, s_q), [od_hl, q_merged])
 
             if "position_dim" in opt:
@@ -480,6 +484,26 @@ class SDNet(nn.Module):
         score_s = trunk(q_input, q_raw, q_mask, x_ocr, x_od, ocr_mask, od_mask, ocr_pos, od_pos)
         return score_s, None
 
+    # -- cross-rank layer-norm statistics ----------------------------------------------------------------------
+    def set_ln_groups(self, groups):
+        """opt['dp_global_batch']: ``groups`` = three process groups over the same ranks, one per trunk branch
+        (question, object, OCR - dp.make_ln_groups), or None.  With groups set, the nine whole-tensor layer norms of a forward take
+        the statistics of all ranks' batches together, so a W-rank step at batch B is the single-process step at batch W * B, and
+        every forward (training or evaluation) and every backward is a collective call: all ranks must run the same number of them,
+        on batches of the same size.  Not with the captured trunk (opt['ruart_graph_trunk']): collectives inside a replayed graph."""
+        if groups is not None:
+            groups = tuple(groups)
+            if len(groups) != 3:
+                raise ValueError("set_ln_groups: one process group per trunk branch (question, object, OCR), got %d" % len(groups))
+            if self.opt.get("ruart_graph_trunk", False):
+                raise ValueError("opt['dp_global_batch'] does not combine with opt['ruart_graph_trunk']: the cross-rank layer norms "
+                                 "exchange statistics with collectives, which the captured trunk cannot replay")
+        self.__dict__["_ln_groups"] = groups
+
+    def ln_groups(self):
+        """(question, object, OCR) process groups of the layer norms, (None, None, None) without cross-rank statistics."""
+        return self.__dict__.get("_ln_groups") or (None, None, None)
+
     # -- the dense trunk and its graph capture -------------------------------------------------------------------
     def _trunk_module(self):
         t = self.__dict__.get("_trunk")
@@ -495,6 +519,8 @@ class SDNet(nn.Module):
         trunk.train(self.training)
         if not (self.opt.get("ruart_graph_trunk", False) and self.training and torch.is_grad_enabled()):
             return trunk
+        if self.__dict__.get("_ln_groups") is not None:
+            raise ValueError("opt['dp_global_batch'] does not combine with opt['ruart_graph_trunk'] (SDNet.set_ln_groups)")
         key = tuple((tuple(a.shape), a.dtype, a.requires_grad) for a in args)
         cache = self.__dict__.setdefault("_trunk_graphs", {})
         ent = cache.get(key)

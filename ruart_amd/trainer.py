@@ -9,7 +9,11 @@ optimizer selection by ``opt['optimizer']`` (:307-317), global-norm clipping (:3
 
 New: ``world_size > 1`` => one process per GPU, gradients averaged with RCCL (dp.GradSync) before clipping; every rank
 holds identical parameters, so the step is "N independent B-sample reference steps with averaged gradients"
-(SURVEY.md section 8e).  ``train()`` / ``predict_for_test()`` without arguments follow the reference end to end - vocabulary and
+(SURVEY.md section 8e).  ``opt['dp_global_batch']`` (off by default) makes the W-rank step the single-process step at batch
+W * batch_size instead: the trunk's whole-tensor layer norms take their statistics over all ranks (SDNet.set_ln_groups) and
+``evaluate`` deals the global batches over the ranks and gathers the results back in the single process's order.  With it on,
+``update()``, ``predict()`` and ``evaluate()`` are collective calls: every rank calls them the same number of times, with shards
+of ``batch_size`` samples.  ``train()`` / ``predict_for_test()`` without arguments follow the reference end to end - vocabulary and
 word vectors from ``train_meta.msgpack``, records from ``{train,val,test}-preprocessed.msgpack`` through ``dataset.VQA_Dataset``,
 run folder, best-model checkpoints, ``submission.json`` - and ``train`` also takes any iterable of collated batches.  The offline
 preprocessing itself (spaCy / fastText / detector outputs -> msgpack) stays out of scope.
@@ -27,7 +31,7 @@ import torch.optim as optim
 
 from . import layers as L
 from .batch import VQA_collate, to_device
-from .sampler import VQA_Sampler
+from .sampler import VQA_Sampler, merge_rank_shards
 from .sdnet import SDNet
 
 log = logging.getLogger(__name__)
@@ -191,6 +195,7 @@ class SDNetTrainer(BaseTrainer):
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.process_group = process_group
         self.grad_sync = None
+        self.global_batch = False          # opt['dp_global_batch'] in effect (setup_model)
         self.fixed_answers_len = 0
         self.updates = 0
         self.best_ANLS = self.best_ACC = -1
@@ -198,6 +203,13 @@ class SDNetTrainer(BaseTrainer):
 
     # -- model / optimizer ------------------------------------------------------------------------------------
     def setup_model(self, vocab_embedding):
+        if self.opt.get("dp_global_batch"):
+            if self.opt.get("dp_overlap_backward"):
+                raise ValueError("opt['dp_global_batch'] does not combine with opt['dp_overlap_backward']: the gradient hooks' collectives "
+                                 "would interleave with the layer norms' exchanges in backward")
+            if self.opt.get("ruart_graph_trunk"):
+                raise ValueError("opt['dp_global_batch'] does not combine with opt['ruart_graph_trunk']: the cross-rank layer norms "
+                                 "exchange statistics with collectives, which the captured trunk cannot replay")
         self.train_loss = AverageMeter()
         self.staged = None                 # what update(stage_next=...) staged last
         opt = dict(self.opt)
@@ -243,6 +255,11 @@ class SDNetTrainer(BaseTrainer):
             self.grad_sync = GradSync(self.network, self.opt, group=self.process_group,
                                       pinned_scalar=bool(self.opt.get("dp_pinned_scalar")) and hasattr(self.optimizer, "clip_and_step"))
             self.grad_sync.broadcast_parameters()
+            if self.opt.get("dp_global_batch"):
+                # the step of one process at the global batch: layer-norm statistics over all ranks, one process group per trunk branch
+                from .dp import make_ln_groups
+                self.network.set_ln_groups(make_ln_groups(self.process_group))
+                self.global_batch = True
             # the replicas share their parameters, not their dropout masks: every rank seeded torch identically above (so that the
             # initial weights agree even before the broadcast), which would make all ranks draw the SAME variational-dropout masks
             # step after step.  From here on each rank's generators run their own stream.
@@ -372,10 +389,22 @@ class SDNetTrainer(BaseTrainer):
         st = self._step_stream()
         return torch.cuda.stream(st) if st is not None else contextlib.nullcontext()
 
+    def _global_world(self):
+        """World size of the cross-rank layer norms (1 without opt['dp_global_batch'] in effect)."""
+        return torch.distributed.get_world_size(self.process_group) if self.global_batch else 1
+
+    def _check_shard(self, ocr_list):
+        """opt['dp_global_batch']: the global element count of a layer norm is W times the local one, so every rank's shard must hold
+        batch_size samples (what VQA_Sampler deals, evaluation's wrap-around included)."""
+        if self._global_world() > 1 and len(ocr_list["num_cnt"]) != self.batch_size:
+            raise ValueError("opt['dp_global_batch']: every rank's shard holds batch_size = %d samples, this one %d"
+                             % (self.batch_size, len(ocr_list["num_cnt"])))
+
     def _update(self, batch, batch_i, next_batch, stage_next=None):
         self.network.train()
         self.network.drop_emb = True
         q_list, ocr_list, od_list, targets, extra_info = batch
+        self._check_shard(ocr_list)
         if next_batch is not None:
             self.network.prefetch_bert(next_batch[0], next_batch[1], next_batch[2])
         scores, _ = self.network(q_list, ocr_list, od_list)
@@ -485,6 +514,7 @@ class SDNetTrainer(BaseTrainer):
         self.network.eval()
         self.network.drop_emb = False
         q_list, ocr_list, od_list, gt_list, extra_info = batch
+        self._check_shard(ocr_list)
         if next_batch is not None:
             self.network.prefetch_bert(next_batch[0], next_batch[1], next_batch[2])
         with torch.no_grad():
@@ -528,8 +558,12 @@ class SDNetTrainer(BaseTrainer):
     def _evaluate(self, val_data, batch_i, mode):
         from torch.utils.data import Dataset
         is_dataset = isinstance(val_data, Dataset)
-        loader = self._loader(val_data, VQA_Sampler(val_data, self.opt["max_batch_num"], self.batch_size, False)) if is_dataset \
-            else val_data
+        # opt['dp_global_batch'] over W > 1 ranks: the reference's evaluation stream in global batches of W * batch_size, rank r
+        # predicting global[r::W]; the results are gathered back into the single process's order (sampler.merge_rank_shards)
+        world = self._global_world() if is_dataset else 1
+        rank = torch.distributed.get_rank(self.process_group) if world > 1 else 0
+        loader = self._loader(val_data, VQA_Sampler(val_data, self.opt["max_batch_num"], self.batch_size, False, rank=rank,
+                                                    world_size=world)) if is_dataset else val_data
         loss = ANLS = ACC = n = nb = 0
         res, save_res = [], []
         it = iter(loader)
@@ -543,14 +577,23 @@ class SDNetTrainer(BaseTrainer):
             loss, ANLS, ACC, n, nb = loss + l, ANLS + a, ACC + c, n + len(r), nb + 1
             res.extend(r)
             save_res.extend(sr)
+        if world > 1:
+            # every rank ends with the same global sums and lists (added in rank order), so no rank's control flow can diverge
+            parts = [None] * world
+            torch.distributed.all_gather_object(parts, (loss, ANLS, ACC, res, save_res), group=self.process_group)
+            loss, ANLS, ACC = (sum(p[k] for p in parts) for k in range(3))
+            loss = loss / world                         # the loss of a global batch is the mean of its W equal shards' losses
+            res = merge_rank_shards([p[3] for p in parts], self.batch_size)
+            save_res = merge_rank_shards([p[4] for p in parts], self.batch_size)
         n_items = len(val_data) if is_dataset else n
         loss, ANLS, ACC = loss / max(nb, 1), ANLS / max(n_items, 1), ACC / max(n_items, 1)
         if not is_dataset or not self._is_main():
             return loss, ANLS, ACC, res
         if mode == "test":
-            end = len(val_data) % self.batch_size
+            gb = self.batch_size * world
+            end = len(val_data) % gb
             if end != 0:
-                res = res[:-(self.batch_size - end)]
+                res = res[:-(gb - end)]
             path = os.path.join(self.saveFolder, "submission.json")
             with open(path, "w") as wf:
                 json.dump(res, wf, indent=2)
