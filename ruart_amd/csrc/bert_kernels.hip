@@ -33,11 +33,7 @@ struct RowStoreSplit {
   unsigned char* o8;
   int H;
   __device__ __forceinline__ void operator()(int c, f32x4_t o) const {
-#if defined(RUART_NT_LN_STORE) && RUART_NT_LN_STORE      // experiments: the fp32 rows (next read: a residual add ~0.6 ms later) past the caches
-    __builtin_nontemporal_store(o, reinterpret_cast<f32x4_t*>(o32 + c));
-#else
     store4(o32 + c, o);
-#endif
     store_split4(o16 + c, o8 + c, H, o);
   }
 };
@@ -90,11 +86,7 @@ __global__ __launch_bounds__(256) void rows_layernorm_kernel(const float* __rest
 #pragma unroll
   for (int i = 0; i < MAXG; ++i) {
     const int c = (i * 64 + lane) * 4;
-#if defined(RUART_NT_LN) && RUART_NT_LN
-    v[i] = (c < H) ? load4_stream(x + (size_t)row * ldx + c) : (f32x4_t){0.f, 0.f, 0.f, 0.f};
-#else
     v[i] = (c < H) ? load4(x + (size_t)row * ldx + c) : (f32x4_t){0.f, 0.f, 0.f, 0.f};
-#endif
   }
   ln_row_finish(v, H, lane, gamma, beta, eps, RowStorePlain<TOut>{out + (size_t)row * ldo});
 }
@@ -110,11 +102,7 @@ __global__ __launch_bounds__(256) void rows_layernorm_split_kernel(const float* 
 #pragma unroll
   for (int i = 0; i < MAXG; ++i) {
     const int c = (i * 64 + lane) * 4;
-#if defined(RUART_NT_LN) && RUART_NT_LN
-    v[i] = (c < H) ? load4_stream(x + (size_t)row * ldx + c) : (f32x4_t){0.f, 0.f, 0.f, 0.f};
-#else
     v[i] = (c < H) ? load4(x + (size_t)row * ldx + c) : (f32x4_t){0.f, 0.f, 0.f, 0.f};
-#endif
   }
   ln_row_finish(v, H, lane, gamma, beta, eps,
                 RowStoreSplit{o32 + (size_t)row * ldo, o16 + (size_t)row * ldo, o8 + (size_t)row * 2 * ldo, H});
@@ -341,17 +329,13 @@ __device__ __forceinline__ void flash_softmax_step(f32x4_t (&sacc)[4], float& m,
     }
 }
 
-// Workgroup -> (block, head) for the MFMA attention kernels.  RUART_ATTN_MAP 1 (default): a 1-D grid, every XCD takes a contiguous
+// Workgroup -> (block, head) for the MFMA attention kernels: a 1-D grid, every XCD takes a contiguous
 // chunk of the logical ids (xcd_remap) and inside it the HEAD index runs fastest (short windows: the 12 x 256-byte slices of a token
 // row are fetched by neighbouring workgroups at the same time instead of by workgroups ~700 launches apart) or, for the long-sequence
 // kernel, the query blocks of one (sequence, head) are neighbours on ONE XCD (they all stream the same K / V rows: the second to
-// fourth reader hits that XCD's L2 instead of the fabric).  0: the 2-D grid (block fastest) of rounds 1-2, kept for A/B runs.
-#ifndef RUART_ATTN_MAP
-#define RUART_ATTN_MAP 1
-#endif
+// fourth reader hits that XCD's L2 instead of the fabric).
 #define ATTN_QGROUP 4
 __device__ __forceinline__ void attn_block_head(int n_heads, bool long_blocks, int n_blocks, int& b, int& h) {
-#if RUART_ATTN_MAP
   const int id = xcd_remap(blockIdx.x, gridDim.x);
   if (!long_blocks) {
     b = id / n_heads;
@@ -364,17 +348,9 @@ __device__ __forceinline__ void attn_block_head(int n_heads, bool long_blocks, i
     h = r / gsz;
     b = first + (r - h * gsz);
   }
-#else
-  b = blockIdx.x;
-  h = blockIdx.y;
-#endif
 }
 static inline dim3 attn_grid(int n_blocks, int n_heads) {
-#if RUART_ATTN_MAP
   return dim3((unsigned)n_blocks * (unsigned)n_heads);
-#else
-  return dim3(n_blocks, n_heads);
-#endif
 }
 
 template <typename T16>
@@ -490,22 +466,14 @@ __global__ __launch_bounds__(256, 2) void attn_flash_kernel(const T16* __restric
 // operand read straight from the packed register: the difference is exact in fp32, so the single rounding to f16 is the one the C++
 // form (f16)(x - (float)hi) makes - same bits, 1.5 instead of 3.25 VALU instructions per element (hipcc converts every element twice
 // and back for that form).  Round 5: these kernels are bound by their VALU issue slots once the loads are out of the way (section 5 (4)).
-#ifndef RUART_ATTN_MIX
-#define RUART_ATTN_MIX 1
-#endif
 __device__ __forceinline__ void split2_f16(float x0, float x1, unsigned& hi2, unsigned& lo2) {
   typedef f16_t f16x2v __attribute__((ext_vector_type(2)));
   const f16x2v h = {(f16_t)x0, (f16_t)x1};
   hi2 = __builtin_bit_cast(unsigned, h);
-#if RUART_ATTN_MIX
   unsigned r;
   asm("v_fma_mixlo_f16 %0, %1, 1.0, -%2 op_sel_hi:[0,0,1]" : "=v"(r) : "v"(x0), "v"(hi2));
   asm("v_fma_mixhi_f16 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(r) : "v"(x1), "v"(hi2));
   lo2 = r;
-#else
-  const f16x2v l = {(f16_t)(x0 - (float)h[0]), (f16_t)(x1 - (float)h[1])};
-  lo2 = __builtin_bit_cast(unsigned, l);
-#endif
 }
 __device__ __forceinline__ void split_f16x4(const f32x4_t a, f16x4_t& hi, f16x4_t& lo) {
   union { f16x4_t v; unsigned u[2]; } h, l;
@@ -525,17 +493,10 @@ __device__ __forceinline__ void split_f16x8(const f32x4_t a, const f32x4_t b, f1
 }
 // lo half of an already rounded pair: lo2 = f16x2(x0 - hi2.lo, x1 - hi2.hi)
 __device__ __forceinline__ unsigned lo2_of(float x0, float x1, unsigned hi2) {
-#if RUART_ATTN_MIX
   unsigned r;
   asm("v_fma_mixlo_f16 %0, %1, 1.0, -%2 op_sel_hi:[0,0,1]" : "=v"(r) : "v"(x0), "v"(hi2));
   asm("v_fma_mixhi_f16 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(r) : "v"(x1), "v"(hi2));
   return r;
-#else
-  typedef f16_t f16x2v __attribute__((ext_vector_type(2)));
-  const f16x2v h = __builtin_bit_cast(f16x2v, hi2);
-  const f16x2v l = {(f16_t)(x0 - (float)h[0]), (f16_t)(x1 - (float)h[1])};
-  return __builtin_bit_cast(unsigned, l);
-#endif
 }
 
 #define ATTN_LD4(p) load4_stream(p)          // the fp32 Q / K / V rows are read once per layer (common.h)
@@ -552,14 +513,6 @@ __global__ __launch_bounds__(256, 2) void attn_flash_split_kernel(const float* _
   __shared__ __attribute__((aligned(16))) float Bs[64];
   __shared__ __attribute__((aligned(16))) int Ls[64];
   typedef f16x8_t frag_t;
-#ifdef RUART_ABL_ATTN_STAMPS           // diagnostic build: s_memrealtime (100 MHz) at five points of every workgroup + its HW_ID
-#define ATTN_STAMP(i) do { if (g_attn_stamps && threadIdx.x == 0) g_attn_stamps[(size_t)blockIdx.x * 8 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-  ATTN_STAMP(0);
-  if (g_attn_stamps && threadIdx.x == 0) g_attn_stamps[(size_t)blockIdx.x * 8 + 6] = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));   // HW_REG_HW_ID
-  if (g_attn_stamps && threadIdx.x == 0) g_attn_stamps[(size_t)blockIdx.x * 8 + 7] = __builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11));  // HW_REG_XCC_ID
-#else
-#define ATTN_STAMP(i)
-#endif
   int b, h;
   attn_block_head(H >> 6, false, 0, b, h);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -568,10 +521,6 @@ __global__ __launch_bounds__(256, 2) void attn_flash_split_kernel(const float* _
   const int tq = q0 + wave * 16 + fr;
   const bool qvalid = tq < q1;
   const int lo_tok = tok_lo[qvalid ? tq : q0];
-#ifdef RUART_ABL_ATTN_STAMPS
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-#endif
-  ATTN_STAMP(1);
 
   // staging K and V: lane -> (row 16 wave + 4 i + lane / 16, 16-byte piece lane % 16): one load instruction covers four whole
   // 256-byte row slices (8 cache lines, every byte used) where the first form - a lane taking 64 contiguous bytes in four
@@ -586,18 +535,9 @@ __global__ __launch_bounds__(256, 2) void attn_flash_split_kernel(const float* _
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int row = wave * 16 + i * 4 + prow;
-#ifdef RUART_ABL_ATTN_L2LOADS        // diagnostic build: every workgroup reads the window of token 0 (L2 hits: the time without HBM reads)
-      const float* kp = qkv + (size_t)(min(row, tn - 1)) * ld + H + h * 64 + piece * 4;
-#else
       const float* kp = qkv + (size_t)(kt + min(row, tn - 1)) * ld + H + h * 64 + piece * 4;      // unconditional (clamped) loads
-#endif
-#ifdef RUART_ABL_ATTN_NOLOADS         // diagnostic build: operands without memory traffic (the kernel's on-chip time)
-      kx[i] = (f32x4_t){(float)((size_t)kp & 255), 1.f, 2.f, 3.f} * 0.01f;
-      vx[i] = (f32x4_t){(float)((size_t)kp & 127), 3.f, 2.f, 1.f} * 0.01f;
-#else
       kx[i] = ATTN_LD4(kp);
       vx[i] = ATTN_LD4(kp + H);
-#endif
     }
     if (tid < 64) {
       const bool in = tid < tn;
@@ -610,13 +550,8 @@ __global__ __launch_bounds__(256, 2) void attn_flash_split_kernel(const float* _
     const float* qp = qkv + (size_t)(qvalid ? tq : q0) * ld + h * 64 + g * 8;
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-#ifdef RUART_ABL_ATTN_NOLOADS
-      qx[2 * ks] = (f32x4_t){(float)((size_t)qp & 255), 1.f, 2.f, 3.f} * 0.01f;
-      qx[2 * ks + 1] = (f32x4_t){(float)((size_t)qp & 63), 1.f, 2.f, 3.f} * 0.01f;
-#else
       qx[2 * ks] = ATTN_LD4(qp + ks * 32);
       qx[2 * ks + 1] = ATTN_LD4(qp + ks * 32 + 4);
-#endif
     }
   }
   load_kv(k0, min(64, k1 - k0));
@@ -634,10 +569,6 @@ __global__ __launch_bounds__(256, 2) void attn_flash_split_kernel(const float* _
       load_kv(kt, tn);
       __syncthreads();                  // every wave is done reading the previous tile's images
     }
-#ifdef RUART_ABL_ATTN_STAMPS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (kt == k0) ATTN_STAMP(2);
-#endif
     {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -645,17 +576,8 @@ __global__ __launch_bounds__(256, 2) void attn_flash_split_kernel(const float* _
         // (rows past the window are clamped copies of its last row - finite - and their keys are masked through Ls = -1: their
         //  probabilities are exactly 0, so they need no zero-fill; 32 selects per thread and step less)
         f16x4_t kh4, kl4, vh4, vl4;
-#ifdef RUART_ABL_ATTN_NOSPLIT        // diagnostic build: the loaded bytes go to LDS as they are (wrong numbers; the time of a kernel whose
-        {                            // producer had written the hi / lo pair itself: 136.9 -> 132.5 us - the split is not what costs)
-          union { f32x4_t f; struct { f16x4_t a, b; } h; } uk, uv;
-          uk.f = kx[i];
-          uv.f = vx[i];
-          kh4 = uk.h.a; kl4 = uk.h.b; vh4 = uv.h.a; vl4 = uv.h.b;
-        }
-#else
         split_f16x4(kx[i], kh4, kl4);
         split_f16x4(vx[i], vh4, vl4);
-#endif
         const int off = row * RS + piece * 8;
         *reinterpret_cast<f16x4_t*>(Kh + off) = kh4;
         *reinterpret_cast<f16x4_t*>(Kl + off) = kl4;
@@ -668,17 +590,6 @@ __global__ __launch_bounds__(256, 2) void attn_flash_split_kernel(const float* _
       }
     }
     __syncthreads();
-#ifdef RUART_ABL_ATTN_STAMPS
-    if (kt == k0) ATTN_STAMP(3);
-#endif
-#ifdef RUART_ABL_ATTN_NOCOMPUTE        // diagnostic build: loads, split and LDS images only (the memory side's own time)
-    l = 1.f;
-    for (int r = 0; r < 64; r += 4)
-      o[0][0] += (float)*reinterpret_cast<const f16_t*>(Kh + r * RS + (tid & 63) * 2) + (float)*reinterpret_cast<const f16_t*>(Kl + r * RS + (tid & 63) * 2) +
-                 (float)*reinterpret_cast<const f16_t*>(Vh + r * RS + (tid & 63) * 2) + (float)*reinterpret_cast<const f16_t*>(Vl + r * RS + (tid & 63) * 2);
-    o[1][1] += qx[0][0] + qx[1][1] + qx[2][2] + qx[3][3];
-    continue;
-#endif
 
     f32x4_t sacc[4];
 #pragma unroll
@@ -729,25 +640,13 @@ __global__ __launch_bounds__(256, 2) void attn_flash_split_kernel(const float* _
         o[dt] = mfma_16x16x32(uh.f, ph[s2], o[dt]);
       }
   }
-  ATTN_STAMP(4);
-#ifdef RUART_ABL_ATTN_TINYSTORE       // diagnostic build: one 2-byte store per workgroup keeps everything before it alive
-  if (tid == 0) ctx16[(size_t)q0 * ldc + h * 64] = (f16_t)(o[0][0] + o[1][1] + o[2][2] + o[3][3] + l);
-  if (qvalid && l == 12345.678f) {
-#elif defined(RUART_ABL_ATTN_NOSTORE)         // diagnostic build: nothing is written (the condition is never true, the compiler cannot know)
-  if (qvalid && l == 12345.678f) {
-#else
   if (qvalid) {
-#endif
     const float inv = 1.0f / l;
     const size_t col = (size_t)h * 64 + g * 4;
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt)
       store_split4(ctx16 + (size_t)tq * ldc + col + dt * 16, ctx8 + (size_t)tq * 2 * ldc + col + dt * 16, H, o[dt] * inv);
   }
-#ifdef RUART_ABL_ATTN_STAMPS
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  ATTN_STAMP(5);
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -796,18 +695,9 @@ __global__ __launch_bounds__(256, 2) void attn_flash_split_mh_kernel(const float
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int row = wave * 16 + i * 4 + prow;
-#ifdef RUART_ABL_ATTN_L2LOADS        // diagnostic build (see the one-head kernel)
-      const float* kp = qkv + (size_t)(min(row, tn - 1)) * ld + H + h * 64 + piece * 4;
-#else
       const float* kp = qkv + (size_t)(kt + min(row, tn - 1)) * ld + H + h * 64 + piece * 4;      // unconditional (clamped) loads
-#endif
-#ifdef RUART_ABL_ATTN_NOLOADS         // diagnostic build: operands without memory traffic (the kernel's on-chip time)
-      kx[i] = (f32x4_t){(float)((size_t)kp & 255), 1.f, 2.f, 3.f} * 0.01f;
-      vx[i] = (f32x4_t){(float)((size_t)kp & 127), 3.f, 2.f, 1.f} * 0.01f;
-#else
       kx[i] = ATTN_LD4(kp);
       vx[i] = ATTN_LD4(kp + H);
-#endif
     }
     if (tid < 64) {
       const bool in = tid < tn;
@@ -819,13 +709,8 @@ __global__ __launch_bounds__(256, 2) void attn_flash_split_mh_kernel(const float
     const float* qp = qkv + (size_t)(qvalid ? tq : q0) * ld + h * 64 + g * 8;
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-#ifdef RUART_ABL_ATTN_NOLOADS
-      qx[2 * ks] = (f32x4_t){(float)((size_t)qp & 255), 1.f, 2.f, 3.f} * 0.01f;
-      qx[2 * ks + 1] = (f32x4_t){(float)((size_t)qp & 63), 1.f, 2.f, 3.f} * 0.01f;
-#else
       qx[2 * ks] = ATTN_LD4(qp + ks * 32);
       qx[2 * ks + 1] = ATTN_LD4(qp + ks * 32 + 4);
-#endif
     }
   };
   load_q(h0);
@@ -834,16 +719,6 @@ __global__ __launch_bounds__(256, 2) void attn_flash_split_mh_kernel(const float
   float m = -1e30f, l = 0.f;
   f32x4_t o[4];
 
-#ifdef RUART_ABL_ATTN_STAMPS           // diagnostic build: slots 0..5 of steps 0..3 (24 values) + HW_ID in slot 30, XCC_ID in 31
-#define MH_STAMP(i) do { if (g_attn_stamps && threadIdx.x == 0 && j < 4) g_attn_stamps[(size_t)blockIdx.x * 32 + j * 6 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-  if (g_attn_stamps && threadIdx.x == 0) {
-    g_attn_stamps[(size_t)blockIdx.x * 32 + 30] = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));
-    g_attn_stamps[(size_t)blockIdx.x * 32 + 31] = __builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11));
-    g_attn_stamps[(size_t)blockIdx.x * 32 + 29] = __builtin_amdgcn_s_memrealtime();
-  }
-#else
-#define MH_STAMP(i)
-#endif
   // a finished head's context rows in their stored form (f16 x 4, e4m3 lo x 4, e4m3 hi x 4 per 16-column group), written one step later
   f16x4_t pend16[4];
   unsigned pend_lo[4], pend_hi[4];
@@ -863,11 +738,6 @@ __global__ __launch_bounds__(256, 2) void attn_flash_split_mh_kernel(const float
   };
   int hh = 0, t = 0;                       // head within the group, key tile within the window
   for (int j = 0; j < n_steps; ++j) {
-    MH_STAMP(0);
-#ifdef RUART_ABL_ATTN_STAMPS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-    MH_STAMP(1);
     const int h = h0 + hh, kt = k0 + t * 64;
     const int tn = min(64, k1 - kt);
     const bool last_tile = t == n_tiles - 1;
@@ -907,7 +777,6 @@ __global__ __launch_bounds__(256, 2) void attn_flash_split_mh_kernel(const float
       if (last_tile) load_q(h + 1);       // the next head's Q rows too (qx is free since this head's split)
     }
     __syncthreads();
-    MH_STAMP(3);
 
     f32x4_t sacc[4];
 #pragma unroll
@@ -968,14 +837,9 @@ __global__ __launch_bounds__(256, 2) void attn_flash_split_mh_kernel(const float
         pend_lo[dt] = pack_fp8x4(lo, (float)(1 << RUART_C8_SA_LO));
         pend_hi[dt] = pack_fp8x4(v, (float)(1 << RUART_C8_SA_HI));
       }
-#ifdef RUART_ABL_ATTN_NOSTORE
-      pend_h = l == 12345.678f ? h : -1;
-#else
       pend_h = h;
-#endif
     }
     __syncthreads();                      // every wave is done reading this step's images
-    MH_STAMP(5);
     t = t_n;
     hh = hh_n;
   }
@@ -983,10 +847,8 @@ __global__ __launch_bounds__(256, 2) void attn_flash_split_mh_kernel(const float
 }
 
 // RUART_ATTN_LONG_WPS: minimum waves per SIMD the register allocator has to leave room for (2: 145 VGPRs, three workgroups per CU;
-// 4: 128 VGPRs with five spilled, four workgroups per CU - A/B builds, tools/r06_attn_long.sh)
-#ifndef RUART_ATTN_LONG_WPS
+// 4: 128 VGPRs with five spilled, four workgroups per CU)
 #define RUART_ATTN_LONG_WPS 2
-#endif
 template <typename T16>
 __global__ __launch_bounds__(256, RUART_ATTN_LONG_WPS) void attn_flash_long_kernel(const T16* __restrict__ qkv, int ld, T16* __restrict__ ctx, int ldc, int H,
                                                                  const int* __restrict__ bq0, const int* __restrict__ bq1,
@@ -1190,9 +1052,7 @@ __global__ __launch_bounds__(256) void pool_mix_cols_kernel(const T* __restrict_
                                                             const int* __restrict__ span_start, const int* __restrict__ span_start_last,
                                                             const int* __restrict__ span_len, const int* __restrict__ dst_row,
                                                             const float* __restrict__ wl, float* __restrict__ out, int ldo, int W, int H) {
-#ifndef RUART_POOL_LB
 #define RUART_POOL_LB 6
-#endif
   constexpr int LB = RUART_POOL_LB;
   const int w = blockIdx.x;
   const int st = span_start[w], n = span_len[w];
@@ -1516,9 +1376,7 @@ __global__ __launch_bounds__(256) void pool_mix_cols_ln_kernel(const float* __re
 // constant: bert-base's 12): the two table loads per layer and lane of the kernel above are as many L1 / L2 transactions as the rows
 // themselves (236 us over the three groups of the bench batch against 194 for the plain kernel); loaded once per workgroup and reused
 // over WPB words they cost a quarter of that.  192 threads (H = 768) x 24 f32x4 = 96 VGPRs of tables.
-#ifndef RUART_POOL_LN_WPB
 #define RUART_POOL_LN_WPB 4
-#endif
 template <int NLT>
 __global__ __launch_bounds__(256) void pool_mix_cols_ln_reg_kernel(const float* __restrict__ layers, size_t layer_stride, int ldl,
                                                                    const int* __restrict__ span_start, const int* __restrict__ span_start_last,
@@ -1552,8 +1410,7 @@ __global__ __launch_bounds__(256) void pool_mix_cols_ln_reg_kernel(const float* 
     // round 6 refuted that - its counted wait was right, loads of both cache policies return in issue order
     // (tools/r06_load_order_probe.hip), a full vmcnt(0) changes nothing - and found that the fault follows the BUILD of that
     // kernel: clean with the values moved to VGPRs (ds_bpermute, or v_mov behind the v_readlane) and clean when the same source is
-    // compiled with -fno-slp-vectorize; DESIGN.md section 5, profiles/r06_readlane_diag.log.  The form stays out; its source is
-    // kept for diagnostic builds under RUART_POOL_RL_DIAG below.)
+    // compiled with -fno-slp-vectorize; DESIGN.md section 5, profiles/r06_readlane_diag.log.  The form stays out.)
     auto stat_of = [&](int l, int p) { return ln.stats[(size_t)l * ln.stats_stride + (l == NLT - 1 ? st_last : st) + min(p, n - 1)]; };
     auto body = [&](auto two_tag) {
       constexpr bool TWO = decltype(two_tag)::value;
@@ -1601,110 +1458,6 @@ __global__ __launch_bounds__(256) void pool_mix_cols_ln_reg_kernel(const float* 
     store4(out + (size_t)dst_row[w] * ldo + col, acc);
   }
 }
-
-#ifdef RUART_POOL_RL_DIAG
-// DIAGNOSTIC BUILDS ONLY (tools/build_variant_all.sh rl -DRUART_POOL_RL_DIAG; tools/r06_readlane_diag.sh): the form of the kernel above that
-// commit 728930f removed - a word's 24 (mu, rstd) pairs fetched by ONE vector load per lane and read back with v_readlane - so that
-// the nondeterminism it was removed for can be examined instead of narrated.  MODE 0: as removed.  MODE 1: a full
-// `s_waitcnt vmcnt(0)` behind the statistics load (if the counted wait the compiler emits were the problem, this form is clean).
-// MODE 2: the row loads with the default cache policy (no mixing of policies in the wave's load queue).  MODE 3: the pairs go through
-// `__shfl` (ds_bpermute) instead of v_readlane (the cross-lane read itself).  MODE 4: v_readlane, its scalar results copied into
-// VGPRs at once.  MODE 5: sixteen wait states behind every pair of v_readlane.  MODE 6: v_readlane, the long-lived copies made by s_mov_b32.
-// Selected with ruart_bert_pool_ln_set_variant(10 + MODE).
-template <int NLT, int MODE>
-__global__ __launch_bounds__(256) void pool_mix_cols_ln_rl_kernel(const float* __restrict__ layers, size_t layer_stride, int ldl,
-                                                                  const int* __restrict__ span_start, const int* __restrict__ span_start_last,
-                                                                  const int* __restrict__ span_len, const int* __restrict__ dst_row,
-                                                                  const float* __restrict__ wl, float* __restrict__ out, int ldo, int W, int H,
-                                                                  PoolLN ln) {
-  constexpr int LB = 6, WPB = RUART_POOL_LN_WPB;
-  static_assert(NLT % LB == 0 && 2 * NLT <= 64, "layers are loaded six at a time; one lane per (layer, piece) statistic");
-  const int col = threadIdx.x * 4;
-  f32x4_t g[NLT], be[NLT];
-  float wgt[NLT];
-  f32x4_t bsum = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int l = 0; l < NLT; ++l) {
-    g[l] = load4(ln.g + (size_t)l * H + col);
-    be[l] = load4(ln.b + (size_t)l * H + col);
-    wgt[l] = wl[l];
-    bsum += be[l] * wgt[l];
-  }
-  auto ldrow = [&](const float* p) { return MODE == 2 ? load4(p) : load4_stream(p); };
-  for (int wi = 0; wi < WPB; ++wi) {
-    const int w = blockIdx.x * WPB + wi;
-    if (w >= W) break;
-    const int st = span_start[w], n = span_len[w];
-    const int st_last = span_start_last ? span_start_last[w] : st;
-    const float inv = 1.0f / (float)n;
-    f32x4_t acc = bsum;
-    const int sl = min((threadIdx.x & 63) >> 1, NLT - 1), sp = min((int)(threadIdx.x & 1), n - 1);
-    const float2 smine = ln.stats[(size_t)sl * ln.stats_stride + (sl == NLT - 1 ? st_last : st) + sp];
-    if (MODE == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    auto stat_of = [&](int l, int p) {
-      if (MODE == 3) return make_float2(__shfl(smine.x, 2 * l + p, 64), __shfl(smine.y, 2 * l + p, 64));
-      int rx = __builtin_amdgcn_readlane(__builtin_bit_cast(int, smine.x), 2 * l + p);
-      int ry = __builtin_amdgcn_readlane(__builtin_bit_cast(int, smine.y), 2 * l + p);
-      if (MODE == 4) {                  // the scalar results copied into VGPRs at once: no SGPR holds a statistic beyond two instructions
-        int vx, vy;
-        asm volatile("v_mov_b32 %0, %2\n\tv_mov_b32 %1, %3" : "=v"(vx), "=v"(vy) : "s"(rx), "s"(ry));
-        return make_float2(__builtin_bit_cast(float, vx), __builtin_bit_cast(float, vy));
-      }
-      if (MODE == 5) asm volatile("s_nop 7\n\ts_nop 7" : "+s"(rx), "+s"(ry));      // sixteen wait states between v_readlane and any reader of its SGPRs
-      if (MODE == 6) {                  // the long-lived copies are written by the SCALAR unit (s_mov_b32), the v_readlane results die at once
-        int cx, cy;
-        asm volatile("s_mov_b32 %0, %2\n\ts_mov_b32 %1, %3" : "=s"(cx), "=s"(cy) : "s"(rx), "s"(ry));
-        return make_float2(__builtin_bit_cast(float, cx), __builtin_bit_cast(float, cy));
-      }
-      return make_float2(__builtin_bit_cast(float, rx), __builtin_bit_cast(float, ry));
-    };
-    auto body = [&](auto two_tag) {
-      constexpr bool TWO = decltype(two_tag)::value;
-#pragma unroll
-      for (int lb = 0; lb < NLT; lb += LB) {
-        f32x4_t v[LB][TWO ? 2 : 1];
-#pragma unroll
-        for (int j = 0; j < LB; ++j) {
-          const int l = lb + j;
-          const int r0 = (l == NLT - 1 ? st_last : st);
-          const float* base = layers + (size_t)l * layer_stride + (size_t)r0 * ldl + col;
-          v[j][0] = ldrow(base);
-          if (TWO) v[j][TWO ? 1 : 0] = ldrow(base + (size_t)ldl);
-        }
-#pragma unroll
-        for (int j = 0; j < LB; ++j) {
-          const float2 s0 = stat_of(lb + j, 0), s1 = stat_of(lb + j, TWO ? 1 : 0);
-          f32x4_t x;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            x[r] = (v[j][0][r] - s0.x) * s0.y;
-            if (TWO) x[r] += (v[j][TWO ? 1 : 0][r] - s1.x) * s1.y;
-          }
-          acc += (x * g[lb + j]) * (wgt[lb + j] * inv);
-        }
-        if (TWO && n > 2) {
-#pragma unroll
-          for (int j = 0; j < LB; ++j) {
-            const int r0 = (lb + j == NLT - 1 ? st_last : st);
-            const float* base = layers + (size_t)(lb + j) * layer_stride + (size_t)r0 * ldl + col;
-            for (int p = 2; p < n; ++p) {
-              const float2 s2 = ln.stats[(size_t)(lb + j) * ln.stats_stride + r0 + p];
-              const f32x4_t y = ldrow(base + (size_t)p * ldl);
-              f32x4_t x;
-#pragma unroll
-              for (int r = 0; r < 4; ++r) x[r] = (y[r] - s2.x) * s2.y;
-              acc += (x * g[lb + j]) * (wgt[lb + j] * inv);
-            }
-          }
-        }
-      }
-    };
-    if (n > 1) body(std::true_type{});
-    else body(std::false_type{});
-    store4(out + (size_t)dst_row[w] * ldo + col, acc);
-  }
-}
-#endif
 
 // d(loss)/d(wl[l]) partial of one word over pre-LayerNorm rows: <grad_out[dst_row[w]], gamma_l (mean of the word's normalised rows) + beta_l>
 template <int NG>
@@ -1842,9 +1595,6 @@ extern "C" int ruart_rows_stats_finish(const float* part, int np, int rows, floa
 
 static int g_pool_ln_reg = 1;      // 1: twelve-layer encoders take the register-table form of the pooling kernel (0: A/B runs)
 extern "C" int ruart_bert_pool_ln_set_variant(int reg_tables) {
-#ifdef RUART_POOL_RL_DIAG
-  if (reg_tables >= 10 && reg_tables <= 16) { g_pool_ln_reg = reg_tables; return 0; }      // diagnostic builds: the removed readlane forms
-#endif
   g_pool_ln_reg = reg_tables < 0 ? 0 : (reg_tables > 2 ? 2 : reg_tables);      // 2: the backward's register-table form too (slower, A/B runs)
   return 0;
 }
@@ -1856,16 +1606,6 @@ extern "C" int ruart_bert_pool_mix_ln(const float* layers_pre, long long layer_s
   if (H % 256 || H <= 0 || H > 1024 || n_words <= 0 || n_layers > POOL_MAX_LAYERS || n_layers <= 0 || !ln_stats || !ln_gamma || !ln_beta)
     return (int)hipErrorInvalidValue;
   const PoolLN ln{(const float2*)ln_stats, (size_t)stats_stride, ln_gamma, ln_beta};
-#ifdef RUART_POOL_RL_DIAG
-#define RL_LAUNCH(MODE) hipLaunchKernelGGL((pool_mix_cols_ln_rl_kernel<12, MODE>), dim3(ceil_div(n_words, RUART_POOL_LN_WPB)), dim3(H / 4), 0, (hipStream_t)stream, layers_pre, (size_t)layer_stride, ldl, span_start, span_start_last, span_len, dst_row, layer_w, out, ldo, n_words, H, ln)
-  if (n_layers == 12 && g_pool_ln_reg >= 10) {
-    switch (g_pool_ln_reg) { case 10: RL_LAUNCH(0); break; case 11: RL_LAUNCH(1); break; case 12: RL_LAUNCH(2); break; case 13: RL_LAUNCH(3); break;
-                             case 14: RL_LAUNCH(4); break; case 15: RL_LAUNCH(5); break; default: RL_LAUNCH(6); }
-    RUART_CHECK_LAUNCH();
-    return 0;
-  }
-#undef RL_LAUNCH
-#endif
   if (n_layers == 12 && g_pool_ln_reg)
     hipLaunchKernelGGL(pool_mix_cols_ln_reg_kernel<12>, dim3(ceil_div(n_words, RUART_POOL_LN_WPB)), dim3(H / 4), 0, (hipStream_t)stream, layers_pre,
                        (size_t)layer_stride, ldl, span_start, span_start_last, span_len, dst_row, layer_w, out, ldo, n_words, H, ln);

@@ -73,16 +73,8 @@ __device__ __forceinline__ f32x4_t load4(const float* p) { return *reinterpret_c
 // Once-read streams (the encoder's fp32 Q / K / V rows in the attention kernel, the twelve layer matrices in sub-word pooling): the
 // non-temporal cache policy.  With the default policy every line of such a stream is allocated in L2 and the Infinity Cache and pushes
 // out lines other kernels still want; measured on attn_flash_split_kernel: 155 -> 124-131 us per call (profiles/r05_attn_split_nt.log).
-// RUART_NT_STREAM=0 (a -D flag) restores the default policy everywhere (A/B builds).
-#ifndef RUART_NT_STREAM
-#define RUART_NT_STREAM 1
-#endif
 __device__ __forceinline__ f32x4_t load4_stream(const float* p) {
-#if RUART_NT_STREAM
   return __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(p));
-#else
-  return load4(p);
-#endif
 }
 __device__ __forceinline__ f32x4_t load4(const bf16_t* p) {
   bf16x4_t v = *reinterpret_cast<const bf16x4_t*>(p);
@@ -95,22 +87,14 @@ __device__ __forceinline__ f32x4_t load4(const f16_t* p) {
   return r;
 }
 __device__ __forceinline__ f32x4_t load4_stream(const bf16_t* p) {
-#if RUART_NT_STREAM
   bf16x4_t v = __builtin_nontemporal_load(reinterpret_cast<const bf16x4_t*>(p));
   f32x4_t r = {(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
   return r;
-#else
-  return load4(p);
-#endif
 }
 __device__ __forceinline__ f32x4_t load4_stream(const f16_t* p) {
-#if RUART_NT_STREAM
   f16x4_t v = __builtin_nontemporal_load(reinterpret_cast<const f16x4_t*>(p));
   f32x4_t r = {(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
   return r;
-#else
-  return load4(p);
-#endif
 }
 __device__ __forceinline__ void store4(f16_t* p, f32x4_t v) {
   f16x4_t r = {(f16_t)v[0], (f16_t)v[1], (f16_t)v[2], (f16_t)v[3]};
@@ -153,12 +137,8 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 // (a few LayerNorm gains x 10-30: layer outputs up to |v| ~ 450, tests/golden/sdnet_e2e_outliers.npz) saturated both activation
 // companions and the probabilities were off by 1.85e-3; with the wider range that fixture holds 1.6e-4 and the N(0, s) goldens are
 // unchanged to within their noise (bench B = 64: 3.9e-5, ragged: 3.3e-4, stress: 1.4e-5).
-#ifndef RUART_C8_SA_LO
 #define RUART_C8_SA_LO 11
-#endif
-#ifndef RUART_C8_SA_HI
 #define RUART_C8_SA_HI 0
-#endif
 #define RUART_C8_SW_HI 7
 #define RUART_C8_SW_LO (RUART_C8_SA_LO + RUART_C8_SW_HI - RUART_C8_SA_HI)
 #define RUART_C8_SHIFT (RUART_C8_SA_LO + RUART_C8_SW_HI)
@@ -201,28 +181,16 @@ __device__ __forceinline__ float sub_f16_hi(float x, unsigned h2) {
   asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(r) : "v"(x), "v"(h2));
   return r;
 }
-// RUART_SPLIT_FAST=0 (a -D flag): the round-2 instruction sequence of the split stores (A/B builds); the bytes are the same
-#ifndef RUART_SPLIT_FAST
-#define RUART_SPLIT_FAST 1
-#endif
 // the three parts of 4 consecutive values in the split form: f16 x 4 (two packed words), the lo8 word, the hi8 word
 __device__ __forceinline__ void split4_words(f32x4_t v, unsigned& h01, unsigned& h23, unsigned& lo8, unsigned& hi8) {
   typedef f16_t f16x2v __attribute__((ext_vector_type(2)));
   const f16x2v a = {(f16_t)v[0], (f16_t)v[1]}, b = {(f16_t)v[2], (f16_t)v[3]};
   h01 = __builtin_bit_cast(unsigned, a);
   h23 = __builtin_bit_cast(unsigned, b);
-#if RUART_SPLIT_FAST
   const f32x4_t lo = {sub_f16_lo(v[0], h01), sub_f16_hi(v[1], h01), sub_f16_lo(v[2], h23), sub_f16_hi(v[3], h23)};
   lo8 = pack_fp8x4_shift<RUART_C8_SA_LO>(lo);
-#else
-  const f32x4_t lo = {v[0] - (float)a[0], v[1] - (float)a[1], v[2] - (float)b[0], v[3] - (float)b[1]};
-  lo8 = pack_fp8x4(lo, (float)(1 << RUART_C8_SA_LO));
-#endif
-#if RUART_C8_SA_HI == 0
+  static_assert(RUART_C8_SA_HI == 0, "hi8 is packed with scale 2^SA_HI == 1");
   hi8 = pack_fp8x4(v, 1.0f);
-#else
-  hi8 = pack_fp8x4(v, (float)(1 << RUART_C8_SA_HI));
-#endif
 }
 // store 4 consecutive values in the split form: p16 -> f16 row, p8 -> the row's lo8 bytes, p8 + hi_off -> its hi8 bytes
 __device__ __forceinline__ void store_split4(f16_t* p16, unsigned char* p8, int hi_off, f32x4_t v) {
@@ -233,16 +201,6 @@ __device__ __forceinline__ void store_split4(f16_t* p16, unsigned char* p8, int 
   *reinterpret_cast<u32x2_t*>(p16) = h;
   *reinterpret_cast<unsigned*>(p8) = lo8;
   *reinterpret_cast<unsigned*>(p8 + hi_off) = hi8;
-}
-// Timing diagnostic (-DRUART_ABL_SPLIT8 in gemm_corr.hip; WRONG operand layout): both companions in one 8-byte store at p8x2 = the
-// row's byte 2 * column - what a [lo4 | hi4]-interleaved companion layout would allow.
-__device__ __forceinline__ void store_split8_diag(f16_t* p16, unsigned char* p8x2, f32x4_t v) {
-  typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-  const f16x4_t h = {(f16_t)v[0], (f16_t)v[1], (f16_t)v[2], (f16_t)v[3]};
-  *reinterpret_cast<f16x4_t*>(p16) = h;
-  const f32x4_t lo = {v[0] - (float)h[0], v[1] - (float)h[1], v[2] - (float)h[2], v[3] - (float)h[3]};
-  const u32x2_t w = {pack_fp8x4(lo, (float)(1 << RUART_C8_SA_LO)), pack_fp8x4(v, (float)(1 << RUART_C8_SA_HI))};
-  *reinterpret_cast<u32x2_t*>(p8x2) = w;
 }
 
 // ---- dropout without stored masks: a counter-based hash of (stream seed, element index) decides every element, so the backward

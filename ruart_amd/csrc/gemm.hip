@@ -154,12 +154,6 @@ __global__ __launch_bounds__(256) void gemm_16_nt_128(const T16* __restrict__ A,
 // ------------------------------------------------------------------------------------------------
 #define BM4 256
 #define BN4 256
-// Counted waits of the four-phase loop (gemm_16_nt_256p8): 1 = three waits per K-tile, each in front of the phase that precedes the
-// first read of what it covers, five half-tiles in flight; 0 = one wait per K-tile for the whole next tile (the product).  Round 6: equal
-// times (gemm_corr.hip has the numbers); diagnostic build only.
-#ifndef RUART_P8_WAITS
-#define RUART_P8_WAITS 0
-#endif
 template <typename T16, bool OUT_F32, int RES, int ACT>
 __global__ __launch_bounds__(512, 2) void gemm_16_nt_256sq(const T16* __restrict__ A, int lda, const T16* __restrict__ W, int ldw,
                                                            const float* __restrict__ bias, const void* __restrict__ R, int ldr,
@@ -458,17 +452,7 @@ __global__ __launch_bounds__(512, 2) void gemm_16_nt_256p8(const T16* __restrict
                                                            const float* __restrict__ bias, const void* __restrict__ R, int ldr,
                                                            void* __restrict__ C, int ldc, int M, int N, int K, int order, int kchunk,
                                                            void* __restrict__ C2, float* __restrict__ colpart, int n_full, int S,
-                                                           float* __restrict__ slabs, const CorrFold fold
-#ifdef RUART_P8_STAMPS
-                                                           , unsigned long long* __restrict__ stamps
-#endif
-) {
-#ifdef RUART_P8_STAMPS
-#define P8_STAMP(i) do { if (stamps && threadIdx.x == 0) stamps[blockIdx.x * 4 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define P8_STAMP(i)
-#endif
-  P8_STAMP(0);
+                                                           float* __restrict__ slabs, const CorrFold fold) {
   if (kchunk > 0) {
     // split-K form (weight gradients: small output, K = all token rows): slice blockIdx.y multiplies columns [z * kchunk, ...) of
     // both operands and writes its own fp32 slab z of C; ruart_splitk_reduce adds the slabs in slice order
@@ -485,12 +469,6 @@ __global__ __launch_bounds__(512, 2) void gemm_16_nt_256p8(const T16* __restrict
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // scalar: wave-dependent offsets stay in SGPRs
   const int wm = wave >> 2, wn = wave & 3;
-#ifndef RUART_P8_ABLATE
-#define RUART_P8_ABLATE 0
-#endif
-  // diagnostic builds only (hipcc -DRUART_P8_ABLATE=n): 1 no prefetch issue in the loop, 2 no fragment reads after the first
-  // K-tile, 4 no stagger, 16 prefetch issued between the MFMAs instead of in the read segment.  0 in production.
-  constexpr int ab = RUART_P8_ABLATE;
   const int ntn = N / BN4, ntm = M / BM4;
   // Workgroups [0, n_full) own whole tiles (XCD-contiguous walk); the rest of the grid are the K slices of the last tiles - the tail
   // split of the launcher (p8_tail_plan, as in gemm_corr.hip): S workgroups per tile, dispatched last, each over nt / S K-tiles,
@@ -556,9 +534,9 @@ __global__ __launch_bounds__(512, 2) void gemm_16_nt_256p8(const T16* __restrict
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) wf[i][ks] = *reinterpret_cast<const frag_t*>(sw + lds_off(wn * 32 + i * 16 + fr, ks * 4 + fq));
   };
-  // 16 MFMAs of one quadrant.  Diagnostic build RUART_P8_ABLATE=16 issues the phase's prefetch (``pre``) between them
-  // instead of in the read segment: measured 4 % SLOWER on the BERT shapes and 2.5 % slower at 4096^3, so it is off.
-  auto quad = [&](int hc, int hr, frag_t (&wf)[2][2], auto pre) {
+  // 16 MFMAs of one quadrant.  (Issuing the phase's prefetch between them instead of in the read segment measured 4 % SLOWER on the
+  // BERT shapes and 2.5 % slower at 4096^3.)
+  auto quad = [&](int hc, int hr, frag_t (&wf)[2][2]) {
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
@@ -566,143 +544,50 @@ __global__ __launch_bounds__(512, 2) void gemm_16_nt_256p8(const T16* __restrict
       for (int j = 0; j < 4; ++j)
 #pragma unroll
         for (int i = 0; i < 2; ++i) acc[hc * 2 + i][hr * 4 + j] = mfma_16x16x32(wf[i][ks], af[j][ks], acc[hc * 2 + i][hr * 4 + j]);
-      if (ks == 0 && (ab & 16)) {
-        __builtin_amdgcn_sched_barrier(0);
-        pre();
-        __builtin_amdgcn_sched_barrier(0);
-      }
     }
     __builtin_amdgcn_s_setprio(0);
   };
-  auto nothing = [] {};
   // one K-tile = four phases.  D: LDS buffer of this tile; N1: K-tile t+1 exists; N2: K-tile t+2 exists.
-  // RUART_P8_BALANCED=1 (diagnostic builds): the read balancing that gemm_tn.hip ships.  Here it measures neutral (layer average 728 us
-  // against 724 us over three interleaved runs of tools/gemm_corr_bench.py), so the plain schedule below stays the product.
-  // RUART_P8_FULLWAIT=0 (diagnostic builds) drops the full LDS wait behind each phase's first barrier and lets the compiler's own
-  // per-fragment waits start the MFMAs as the fragments arrive: measured neutral (712-721 vs 716 us per layer), so the waits stay.
-#ifndef RUART_P8_FULLWAIT
-#define RUART_P8_FULLWAIT 1
-#endif
-#ifndef RUART_P8_BALANCED
-#define RUART_P8_BALANCED 0
-#endif
-#if RUART_P8_BALANCED
-  // Fragment reads per phase 8 / 4 / 8 / 4 (ds_read_b128) instead of 12 / 4 / 8 / 0: phase 3, which has nothing of its own to fetch,
-  // reads the NEXT K-tile's W-h0 fragments into the register set that held this tile's W-h1 (dead after phase 2) - the two sets swap
-  // roles with the LDS buffer, no register is added - so the longest read segment of the loop is a third shorter.  K-tile t+1's W-h0 must then have landed for BOTH wave groups one barrier
-  // earlier than the rest of that tile: the counted wait at the end of phase 2 (the five half-tiles issued after it may still be in
-  // flight) stands before the barrier the other group pairs with.  Same products in the same order: bitwise the old kernel.
+  // The read balancing that gemm_tn.hip ships measures neutral here (layer average 728 us against 724 us over three interleaved runs of
+  // tools/gemm_corr_bench.py), and so does dropping the full LDS wait behind each phase's first barrier (712-721 vs 716 us per layer).
   auto tile = [&](auto dtag, auto n1tag, auto n2tag, int t) {
     constexpr int D = decltype(dtag)::value;
     constexpr bool N1 = decltype(n1tag)::value, N2 = decltype(n2tag)::value;
-    constexpr bool S1 = N1 && !(ab & 1), S2 = N2 && !(ab & 1);
-    const bool rd = !(ab & 2) || t == 0;
-    auto run = [&](frag_t (&wc)[2][2], frag_t (&wn)[2][2]) {
-      // phase 0: quadrant (rows h0, cols h0), W-h0 fragments already in wc; prefetch (t+1, A-h1)
-      if (rd) read_a(D, 0);
-      if (S1) stage_a(D ^ 1, 1, t + 1);
-      RUART_BAR();
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      quad(0, 0, wc, nothing);
-      RUART_BAR();
-      // phase 1: (rows h0, cols h1); prefetch (t+2, W-h0)
-      if (rd) read_w(D, 1, wn);
-      if (S2) stage_w(D, 0, t + 2);
-      RUART_BAR();
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      quad(1, 0, wn, nothing);
-      RUART_BAR();
-      // phase 2: (rows h1, cols h1); prefetch (t+2, A-h0)
-      if (rd) read_a(D, 1);
-      if (S2) stage_a(D, 0, t + 2);
-      RUART_BAR();
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      quad(1, 1, wn, nothing);
-      if (N2) {
-        asm volatile("s_waitcnt vmcnt(10)" ::: "memory");    // (t+1, W-h0) has landed; the five half-tiles issued after it may be in flight
-      } else if (N1) {
-        asm volatile("s_waitcnt vmcnt(2)" ::: "memory");     // tail: only (t+1, A-h1) is younger
-      }
-      RUART_BAR();
-      // phase 3: (rows h1, cols h0) - operands in registers; prefetch (t+2, W-h1); read (t+1, W-h0) for the next tile's phase 0
-      if (N2) {
-        if (S2) stage_w(D, 1, t + 2);
-        asm volatile("s_waitcnt vmcnt(6)" ::: "memory");     // K-tile t+1 complete; the 3 youngest half-tiles stay in flight
-      } else if (N1) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // last prefetch: (t+1, A-h1) from phase 0
-      }
-      RUART_BAR();
-      if (N1 && rd) read_w(D ^ 1, 0, wn);
-      quad(0, 1, wc, nothing);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // (free: issued 16 MFMAs ago) the W-h0 slot is restaged two barriers on
-      RUART_BAR();
-    };
-    if constexpr (D == 0) run(wf0, wf1); else run(wf1, wf0);
-  };
-#else
-  auto tile = [&](auto dtag, auto n1tag, auto n2tag, int t) {
-    constexpr int D = decltype(dtag)::value;
-    constexpr bool N1 = decltype(n1tag)::value, N2 = decltype(n2tag)::value;
-    constexpr bool S1 = N1 && !(ab & 1), S2 = N2 && !(ab & 1);
-    const bool rd = !(ab & 2) || t == 0;
     // phase 0: quadrant (rows h0, cols h0); prefetch (t+1, A-h1)
-    if (rd) read_w(D, 0, wf0);
+    read_w(D, 0, wf0);
     __builtin_amdgcn_sched_barrier(0);
-    if (rd) read_a(D, 0);
-    if (S1 && !(ab & 16)) stage_a(D ^ 1, 1, t + 1);
-#if RUART_P8_WAITS
-    // (this tile's W-h1, read one phase on, has landed; five younger half-tiles may be in flight)
-    if (N1) asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-#endif
+    read_a(D, 0);
+    if (N1) stage_a(D ^ 1, 1, t + 1);
     asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");     // the 4 W-h0 reads (issued first) are back: its slot may be restaged
     RUART_BAR();
-    if (RUART_P8_FULLWAIT) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (S1) quad(0, 0, wf0, [&] { stage_a(D ^ 1, 1, t + 1); }); else quad(0, 0, wf0, nothing);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    quad(0, 0, wf0);
     RUART_BAR();
     // phase 1: (rows h0, cols h1); prefetch (t+2, W-h0)
-    if (rd) read_w(D, 1, wf1);
-    if (S2 && !(ab & 16)) stage_w(D, 0, t + 2);
-#if RUART_P8_WAITS
-    // (this tile's A-h1 has landed)
-    if (N2) asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); else if (N1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
+    read_w(D, 1, wf1);
+    if (N2) stage_w(D, 0, t + 2);
     RUART_BAR();
-    if (RUART_P8_FULLWAIT) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (S2) quad(1, 0, wf1, [&] { stage_w(D, 0, t + 2); }); else quad(1, 0, wf1, nothing);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    quad(1, 0, wf1);
     RUART_BAR();
     // phase 2: (rows h1, cols h1); prefetch (t+2, A-h0)
-    if (rd) read_a(D, 1);
-    if (S2 && !(ab & 16)) stage_a(D, 0, t + 2);
+    read_a(D, 1);
+    if (N2) stage_a(D, 0, t + 2);
     RUART_BAR();
-    if (RUART_P8_FULLWAIT) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (S2) quad(1, 1, wf1, [&] { stage_a(D, 0, t + 2); }); else quad(1, 1, wf1, nothing);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    quad(1, 1, wf1);
     RUART_BAR();
     // phase 3: (rows h1, cols h0) - operands already in registers; prefetch (t+2, W-h1)
-#if RUART_P8_WAITS
-    // (K-tile t+1's W-h0 and A-h0 have landed)
     if (N2) {
-      if (S2) stage_w(D, 1, t + 2);
-      asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-    } else if (N1) {
-      asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    }
-#else
-    if (N2) {
-      if (!(ab & 16)) {
-        if (S2) stage_w(D, 1, t + 2);
-        asm volatile("s_waitcnt vmcnt(6)" ::: "memory");   // K-tile t+1 complete; the 3 youngest half-tiles stay in flight
-      } else {
-        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");   // (diagnostic placement: this phase's prefetch follows the wait)
-      }
+      stage_w(D, 1, t + 2);
+      asm volatile("s_waitcnt vmcnt(6)" ::: "memory");     // K-tile t+1 complete; the 3 youngest half-tiles stay in flight
     } else if (N1) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // last prefetch: (t+1, A-h1) from phase 0
     }
-#endif
     RUART_BAR();
-    if (S2) quad(0, 1, wf0, [&] { stage_w(D, 1, t + 2); }); else quad(0, 1, wf0, nothing);
+    quad(0, 1, wf0);
     RUART_BAR();
   };
-#endif
   using I0 = std::integral_constant<int, 0>;
   using I1 = std::integral_constant<int, 1>;
   using Tt = std::true_type;
@@ -722,17 +607,9 @@ __global__ __launch_bounds__(512, 2) void gemm_16_nt_256p8(const T16* __restrict
   stage_w(1, 0, kb + 1);
   stage_a(1, 0, kb + 1);
   stage_w(1, 1, kb + 1);
-#if RUART_P8_WAITS
-  asm volatile("s_waitcnt vmcnt(10)" ::: "memory");          // K-tile kb's W-h0 and A-h0 landed (this wave's share)
-#else
   asm volatile("s_waitcnt vmcnt(6)" ::: "memory");           // K-tile kb landed (this wave's share)
-#endif
   RUART_BAR();
-  P8_STAMP(1);
-#if RUART_P8_BALANCED
-  read_w(0, 0, wf0);
-#endif
-  if (wave >= 4 && !(ab & 4)) RUART_BAR();   // stagger: waves 4-7 run one barrier behind
+  if (wave >= 4) RUART_BAR();   // stagger: waves 4-7 run one barrier behind
   int t = kb;
   for (; t + 2 < ke; t += 2) {
     tile(I0{}, Tt{}, Tt{}, t);
@@ -740,9 +617,8 @@ __global__ __launch_bounds__(512, 2) void gemm_16_nt_256p8(const T16* __restrict
   }
   tile(I0{}, Tt{}, Ff{}, t);
   tile(I1{}, Ff{}, Ff{}, t + 1);
-  if (wave < 4 && !(ab & 4)) RUART_BAR();    // waves 0-3 pair the lagging group's last barrier
+  if (wave < 4) RUART_BAR();    // waves 0-3 pair the lagging group's last barrier
   RUART_BAR();                                                  // every wave is done reading operand tiles
-  P8_STAMP(2);
 
   if (slice >= 0) {
     // partial sums of this slice, thread-major ([i][j][tid] x 4 floats: 16-byte coalesced stores, read back the same way)
@@ -754,10 +630,6 @@ __global__ __launch_bounds__(512, 2) void gemm_16_nt_256p8(const T16* __restrict
     return;
   }
   p8_epilogue<T16, OUT_F32, RES, ACT, FK>(acc, smem, m0, n0, tm, bias, R, ldr, C, ldc, N, C2, colpart, 0, 4, fold);
-#ifdef RUART_P8_STAMPS
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-  P8_STAMP(3);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -865,11 +737,6 @@ size_t g_prof_used = 0;
 bool g_prof_on = false;
 bool g_prof_marks_only = false;      // ruart_prof_enable(2): markers are recorded, the GEMM launches are not bracketed
 }  // namespace
-#ifdef RUART_P8_STAMPS
-unsigned long long* g_p8_stamps = nullptr;   // diagnostic build only: 4 x s_memrealtime per workgroup
-extern "C" int ruart_gemm_set_stamps(unsigned long long* p) {
-  RUART_ENTRY(); g_p8_stamps = p; return 0; }
-#endif
 int g_tile_order = 8;            // GROUP_M of the tile walk (0 = plain row-major); tuning knob, see ruart_gemm_set_tile_order
 int g_tile_order_auto = 1;       // the fp16c kernel picks GROUP_M per shape until ruart_gemm_set_tile_order is called (gemm_corr.hip)
 int ruart_prof_real_rows = 0;   // set by ruart_bert_forward: algorithmic row count (the GEMM itself runs on padded rows)
@@ -992,9 +859,6 @@ __device__ __forceinline__ void mfma_agpr(const bf16x8_t& a, const bf16x8_t& b, 
   asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
 }
 
-#ifndef RUART_W4_DMA_EARLY
-#define RUART_W4_DMA_EARLY 0
-#endif
 template <typename T16, bool OUT_F32, int RES, int ACT>
 __global__ __launch_bounds__(256, 1) void gemm_16_nt_256w4(const T16* __restrict__ A, int lda, const T16* __restrict__ W, int ldw,
                                                            const float* __restrict__ bias, const void* __restrict__ R, int ldr,
@@ -1051,14 +915,7 @@ __global__ __launch_bounds__(256, 1) void gemm_16_nt_256w4(const T16* __restrict
       }
       __builtin_amdgcn_sched_barrier(0);
       if (RD) rd(nxt, g < 8 ? 8 + g : g - 8, rd_d, rd_ks);
-#if RUART_W4_DMA_EARLY            // (diagnostic builds: both pieces of a pair in the first half of the step - half a step more flight time)
-      if (DMA && g < 8) {
-        piece(dma_d, 2 * g, dma_kt);
-        piece(dma_d, 2 * g + 1, dma_kt);
-      }
-#else
       if (DMA) piece(dma_d, g, dma_kt);
-#endif
       __builtin_amdgcn_sched_barrier(0);
     }
   };
@@ -1239,10 +1096,6 @@ static void launch_one(const T16* a, int lda, const T16* w, int ldw, const float
     auto kern = gemm_16_nt_256p8<T16, OF, RS, AC>;
     static bool done = (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds), true);
     (void)done;
-#ifdef RUART_P8_STAMPS
-    hipLaunchKernelGGL(kern, dim3((M / BM4) * (N / BN4)), dim3(512), lds, s, a, lda, w, ldw, bias, residual, ldr, C, ldc, M, N, K,
-                       g_tile_order, 0, (void*)nullptr, (float*)nullptr, (M / BM4) * (N / BN4), 0, (float*)nullptr, CorrFold{}, g_p8_stamps);
-#else
     // GROUP_M from the tile counts (ruart_tile_group_m, gemm_shared.h) until ruart_gemm_set_tile_order pins a value
     const int order = g_tile_order_auto ? ruart_tile_group_m(M / BM4, N / BN4, K, false) : g_tile_order;
     const int tiles = (M / BM4) * (N / BN4);
@@ -1261,7 +1114,6 @@ static void launch_one(const T16* a, int lda, const T16* w, int ldw, const float
       (void)fdone;
       hipLaunchKernelGGL(fix, dim3(4 * tp.r), dim3(512), flds, s, (const float*)tail_ws, tp.S, tp.n_full, bias, residual, ldr, C, ldc, M, N, order);
     }
-#endif
   } else if (g_gemm_variant >= 3 && sq) {
     auto kern = gemm_16_nt_256sq<T16, OF, RS, AC>;
     static bool done = (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds), true);
@@ -1337,13 +1189,8 @@ static void launch_gelu2(const void* A, int lda, const void* W, int ldw, const f
   auto kern = gemm_16_nt_256p8<T16, false, 0, 2>;
   static bool done = (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds), true);
   (void)done;
-#ifdef RUART_P8_STAMPS
-  hipLaunchKernelGGL(kern, dim3((M / BM4) * (N / BN4)), dim3(512), lds, s, (const T16*)A, lda, (const T16*)W, ldw, bias, (const void*)nullptr, 0, G,
-                     ldc, M, N, K, g_tile_order, 0, Hout, (float*)nullptr, (M / BM4) * (N / BN4), 0, (float*)nullptr, CorrFold{}, (unsigned long long*)nullptr);
-#else
   hipLaunchKernelGGL(kern, dim3((M / BM4) * (N / BN4)), dim3(512), lds, s, (const T16*)A, lda, (const T16*)W, ldw, bias, (const void*)nullptr, 0, G,
                      ldc, M, N, K, g_tile_order, 0, Hout, (float*)nullptr, (M / BM4) * (N / BN4), 0, (float*)nullptr, CorrFold{});
-#endif
 }
 
 extern "C" int ruart_gemm_16_nt_gelu2(const void* A, int lda, const void* W, int ldw, const float* bias, void* H16, void* G16, int ldc, int M,
@@ -1380,13 +1227,8 @@ extern "C" int ruart_gemm_16_nt_gelu_bwd(const void* dY_bf16, int lda, const voi
   static bool done = (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds), true);
   (void)done;
   void* rec = ruart_prof_begin_((hipStream_t)stream, M, N, K);
-#ifdef RUART_P8_STAMPS
-  hipLaunchKernelGGL(kern, dim3((M / BM4) * (N / BN4)), dim3(512), lds, (hipStream_t)stream, (const bf16_t*)dY_bf16, lda, (const bf16_t*)Wt_bf16, ldw,
-                     (const float*)nullptr, H16, ldh, dH_bf16, ldc, M, N, K, g_tile_order, 0, G_bf16, colpart, (M / BM4) * (N / BN4), 0, (float*)nullptr, CorrFold{}, (unsigned long long*)nullptr);
-#else
   hipLaunchKernelGGL(kern, dim3((M / BM4) * (N / BN4)), dim3(512), lds, (hipStream_t)stream, (const bf16_t*)dY_bf16, lda, (const bf16_t*)Wt_bf16, ldw,
                      (const float*)nullptr, H16, ldh, dH_bf16, ldc, M, N, K, g_tile_order, 0, G_bf16, colpart, (M / BM4) * (N / BN4), 0, (float*)nullptr, CorrFold{});
-#endif
   ruart_prof_end_(rec, (hipStream_t)stream);
   RUART_CHECK_LAUNCH();
   return 0;
@@ -1402,13 +1244,8 @@ static void launch_splitk(const void* A, int lda, const void* W, int ldw, float*
   static bool done = (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds), true);
   (void)done;
   const int nz = (K + kchunk - 1) / kchunk;
-#ifdef RUART_P8_STAMPS
-  hipLaunchKernelGGL(kern, dim3((M / BM4) * (N / BN4), nz), dim3(512), lds, s, (const T16*)A, lda, (const T16*)W, ldw, (const float*)nullptr,
-                     (const void*)nullptr, 0, (void*)part, ldc, M, N, K, g_tile_order, kchunk, (void*)nullptr, (float*)nullptr, (M / BM4) * (N / BN4), 0, (float*)nullptr, CorrFold{}, (unsigned long long*)nullptr);
-#else
   hipLaunchKernelGGL(kern, dim3((M / BM4) * (N / BN4), nz), dim3(512), lds, s, (const T16*)A, lda, (const T16*)W, ldw, (const float*)nullptr,
                      (const void*)nullptr, 0, (void*)part, ldc, M, N, K, g_tile_order, kchunk, (void*)nullptr, (float*)nullptr, (M / BM4) * (N / BN4), 0, (float*)nullptr, CorrFold{});
-#endif
 }
 
 // The projections of the LayerNorm-folded plain 16-bit encoder pass (round 6; CorrFold, gemm_shared.h; the fp16c pass's counterpart is
@@ -1439,16 +1276,6 @@ extern "C" int ruart_gemm_16_nt_fold(const void* A, int lda, const void* W, int 
   const int order = g_tile_order_auto ? ruart_tile_group_m(M / BM4, N / BN4, K, false) : g_tile_order;
   const int tiles = (M / BM4) * (N / BN4);
   void* rec = ruart_prof_begin_(s, M, N, K);
-#ifdef RUART_P8_STAMPS
-#define FOLD_LAUNCH(T, RS, AC, FKV)                                                                                                            \
-  do {                                                                                                                                       \
-    auto kern = gemm_16_nt_256p8<T, false, RS, AC, FKV>;                                                                                     \
-    static bool done = (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds), true);                      \
-    (void)done;                                                                                                                              \
-    hipLaunchKernelGGL(kern, dim3(tiles), dim3(512), lds, s, (const T*)A, lda, (const T*)W, ldw, bias, residual, ldr, C, ldc, M, N, K, order, 0, \
-                       (void*)nullptr, (float*)nullptr, tiles, 0, (float*)nullptr, f, g_p8_stamps);                                          \
-  } while (0)
-#else
 #define FOLD_LAUNCH(T, RS, AC, FKV)                                                                                                            \
   do {                                                                                                                                       \
     auto kern = gemm_16_nt_256p8<T, false, RS, AC, FKV>;                                                                                     \
@@ -1457,7 +1284,6 @@ extern "C" int ruart_gemm_16_nt_fold(const void* A, int lda, const void* W, int 
     hipLaunchKernelGGL(kern, dim3(tiles), dim3(512), lds, s, (const T*)A, lda, (const T*)W, ldw, bias, residual, ldr, C, ldc, M, N, K, order, 0, \
                        (void*)nullptr, (float*)nullptr, tiles, 0, (float*)nullptr, f);                                                       \
   } while (0)
-#endif
   if (dtype == RUART_DT_F16) {
     if (kind == 3) FOLD_LAUNCH(f16_t, 1, 0, 3);
     else if (kind == 2) FOLD_LAUNCH(f16_t, 0, 1, 1);

@@ -27,19 +27,9 @@
 typedef int i32x4_t __attribute__((ext_vector_type(4)));
 typedef int i32x8_t __attribute__((ext_vector_type(8)));
 
-// operand format code of the scaled MFMA: 0 = e4m3 (production).  Diagnostic builds (tools/build_variant.sh fp6 -DRUART_C8_FMT=2)
-// make the instruction read the same registers as e2m3 fp6 - wrong numbers, but the 4x-rate timing of an fp6 correction phase.
-#ifndef RUART_C8_FMT
-#define RUART_C8_FMT 0
-#endif
-
-// Counted waits of the K loop: 0 = one wait per K-tile for the whole next tile (three half-tiles in flight; the product since round 1),
-// 1 = three waits per K-tile, each one phase ahead of the first read of what it covers (five half-tiles in flight, every DMA piece has
-// >= 5 phases to land instead of >= 3).  Round 6 measured 1 against 0: race screen clean, time equal (layer 1 246 vs 1 258 us, step 21.98
-// vs 21.98 ms, profiles/r06_waits_ab.log) - the loop does not wait for its prefetch; kept as a diagnostic build.
-#ifndef RUART_P8_WAITS
-#define RUART_P8_WAITS 0
-#endif
+// Counted waits of the K loop: one wait per K-tile for the whole next tile (three half-tiles in flight).  Three waits per K-tile, each one
+// phase ahead of the first read of what it covers (five half-tiles in flight), measured equal in round 6 (layer 1 246 vs 1 258 us, step
+// 21.98 vs 21.98 ms, profiles/r06_waits_ab.log): the loop does not wait for its prefetch.
 #define CBM 256
 #define CBN 256
 #define CBKB 128   // bytes of one row of one K-tile (64 f16 or 128 fp8)
@@ -48,8 +38,8 @@ typedef int i32x8_t __attribute__((ext_vector_type(8)));
 // degree-7 fit of log2(0.5 erfc(a / sqrt 2)) on a in [0, 7.07] (weighted by erfc, so the ABSOLUTE error of Phi is what is minimised:
 // 7e-8; beyond 7.07 Phi is 0 or 1 to 1e-12 and |x| is clamped).  |GELU error| <= 5.0e-7 over [-12, 12], rms 7.6e-8 on [-4, 4] -
 // the level of the Abramowitz-Stegun 7.1.26 erf this replaces (4.6e-7 / 1.2e-7) with ONE transcendental per element instead of two
-// (v_rcp + v_exp run at a quarter of the fma rate).  Measured on the FFN intermediate dense (43 008 x 3072 x 768, diagnostic builds
-// -DRUART_ABL_NOGELU / -DRUART_ABL_NOFP8): 403 us per launch, 375 without the GELU, 361 without the fp8 companions, 320 without
+// (v_rcp + v_exp run at a quarter of the fma rate).  Measured on the FFN intermediate dense (43 008 x 3072 x 768, ablated
+// builds): 403 us per launch, 375 without the GELU, 361 without the fp8 companions, 320 without
 // both - the A-S form was 405, so the epilogue is not bound by these instructions alone.  The logistic-polynomial form of the plain
 // 16-bit epilogue (3.4e-6) would be the largest error of the whole layer here.
 __device__ __forceinline__ float gelu_erfc7(float x) {
@@ -75,12 +65,6 @@ __device__ __forceinline__ f32x4_t gelu4_as(f32x4_t v) {
 // Epilogue of one 256 x 256 tile through LDS, eight rows per pass (as gemm_16_nt_256p8): bias, then per EPI the residual / GELU + split
 // stores.  Shared by the GEMM kernel and by the fix-up kernel of its split tail tiles.  `smem`: >= 8 x 32 x 272 bytes, no longer read as
 // operand tiles by any wave.
-// Cache policy of the epilogue's streams (experiments, round 5): bit 0 the fp32 QKV rows (394 MB per launch, read once by the attention
-// kernel), bit 1 the fp32 pre-LayerNorm rows of the two N = 768 products, bit 3 their residual loads - non-temporal when set.
-#ifndef RUART_NT_EPI
-#define RUART_NT_EPI 0
-#endif
-
 // (CorrFold, fold_row_stats, row16_sum: gemm_shared.h - the plain 16-bit kernel folds its LayerNorms the same way since round 6)
 // EPI: 0 fp32 out; 1 fp32 out + fp32 residual; 2 GELU, split out; 3 fp32 out + (LayerNorm of the) residual, split out, row partials.
 // FOLD (EPI 0 / 2): the A rows are pre-LayerNorm rows, see CorrFold.
@@ -148,8 +132,7 @@ __device__ __forceinline__ void corr_epilogue(f32x4_t (&acc)[4][8], char* smem, 
     if (EPI == 1 || EPI == 3) {
 #pragma unroll
       for (int rr = 0; rr < 8; ++rr)
-        res[rr] = (RUART_NT_EPI & 8) ? __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(at(R, (e_r + rr * st_r) * 4u)))
-                                     : *reinterpret_cast<const f32x4_t*>(at(R, (e_r + rr * st_r) * 4u));
+        res[rr] = *reinterpret_cast<const f32x4_t*>(at(R, (e_r + rr * st_r) * 4u));
     }
     if constexpr (FOLD) {
       // v = rstd 2^s (acc - mu c) + d   (d arrives as `bias`)
@@ -179,40 +162,24 @@ __device__ __forceinline__ void corr_epilogue(f32x4_t (&acc)[4][8], char* smem, 
         }
         v[rr] += res[rr];
         *reinterpret_cast<f32x4_t*>(atw(C, ec * 4u)) = v[rr];
-#ifdef RUART_ABL_SPLIT8
-        store_split8_diag(C16 + (size_t)ec, C8 + 2 * (size_t)ec, v[rr]);
-#elif !defined(RUART_ABL_FOLD_NOSPLIT)     // (timing diagnostic: kind 3 without its split copy)
         // (a C8 row is 2 ldc bytes: lo8 halves at [0, N), hi8 halves at [N, 2N))
         store_split4(reinterpret_cast<f16_t*>(atw(C16, ec * 2u)), reinterpret_cast<unsigned char*>(atw(C8, ec * 2u - (unsigned)ncol)), N, v[rr]);
-#endif
-#ifndef RUART_ABL_FOLD_NOSTATS        // (timing diagnostic: the epilogue without the rows' partial sums - wrong results downstream)
         const float s1 = row16_sum((v[rr][0] + v[rr][1]) + (v[rr][2] + v[rr][3]));
         const float s2 = row16_sum(fmaf(v[rr][0], v[rr][0], v[rr][1] * v[rr][1]) + fmaf(v[rr][2], v[rr][2], v[rr][3] * v[rr][3]));
         if ((lane & 15) == 0) rpart[hh * 32 + rr * 4] = make_float2(s1, s2);
-#endif
       }
       continue;
     }
-#ifndef RUART_ABL_NOGELU            // (diagnostic builds: the epilogue without its GELU / without its fp8 stores)
     if (EPI == 2) {
 #pragma unroll
       for (int rr = 0; rr < 8; ++rr) v[rr] = gelu4_as(v[rr]);
     }
-#endif
 #pragma unroll
     for (int rr = 0; rr < 8; ++rr) {
       const unsigned ec = e_c + rr * st_c;
       if (EPI == 1) v[rr] += res[rr];
       if (EPI == 2)
-#ifdef RUART_ABL_NOFP8
-        *reinterpret_cast<f16x4_t*>(atw(C, ec * 2u)) = (f16x4_t){(f16_t)v[rr][0], (f16_t)v[rr][1], (f16_t)v[rr][2], (f16_t)v[rr][3]};
-#elif defined(RUART_ABL_SPLIT8)
-        store_split8_diag(reinterpret_cast<f16_t*>(C) + (size_t)ec, C8 + 2 * (size_t)ec, v[rr]);
-#else
         store_split4(reinterpret_cast<f16_t*>(atw(C, ec * 2u)), reinterpret_cast<unsigned char*>(atw(C8, ec * 2u - (unsigned)ncol)), N, v[rr]);
-#endif
-      else if ((EPI == 0 && (RUART_NT_EPI & 1)) || (EPI == 1 && (RUART_NT_EPI & 2)))
-        __builtin_nontemporal_store(v[rr], reinterpret_cast<f32x4_t*>(atw(C, ec * 4u)));
       else
         *reinterpret_cast<f32x4_t*>(atw(C, ec * 4u)) = v[rr];
     }
@@ -243,39 +210,16 @@ __device__ __forceinline__ void corr_tile_of(int id, int ntm, int ntn, int order
   }
 }
 
-// Diagnostic builds (tools/build_variant.sh v224 -DRUART_GEMM_VGPR_HALF=112): cap the kernel at 2 x N architectural VGPRs (hipcc doubles
-// an amdgpu_num_vgpr request on the unified register file of gfx90a+), so that 2 waves per SIMD leave registers for a co-resident small
-// wave of another kernel.  At 224 the compiler spills inside the K loop: not a product setting.
-#ifdef RUART_GEMM_VGPR_HALF
-#define RUART_VGPR_ATTR __attribute__((amdgpu_num_vgpr(RUART_GEMM_VGPR_HALF)))
-#else
-#define RUART_VGPR_ATTR
-#endif
+// (Capped at 224 architectural VGPRs - room for a co-resident small wave of another kernel - the compiler spills inside the K loop:
+// DESIGN.md section 5, round 4.)
 // EPI: 0 fp32 out; 1 fp32 out + fp32 residual; 2 GELU, split out (C = f16 rows, C8 = fp8 rows of 2N bytes)
 template <int EPI, bool FOLD = false>
-__global__ RUART_VGPR_ATTR __launch_bounds__(512, 2) void gemm_16c_nt_256p8(const char* __restrict__ A16, const char* __restrict__ A8, int pitch_a,
+__global__ __launch_bounds__(512, 2) void gemm_16c_nt_256p8(const char* __restrict__ A16, const char* __restrict__ A8, int pitch_a,
                                                             const char* __restrict__ W16, const char* __restrict__ W8, int pitch_w,
                                                             const float* __restrict__ bias, const float* __restrict__ R, int ldr,
                                                             void* __restrict__ C, int ldc, unsigned char* __restrict__ C8, int M, int N,
                                                             int K, int order, int n8, int o8, int n_full, int S,
-                                                            float* __restrict__ slabs, const CorrFold f
-#ifdef RUART_P8_STAMPS
-                                                            , unsigned long long* __restrict__ stamps
-#endif
-) {
-  // diagnostic builds (tools/build_variant.sh stamps -DRUART_P8_STAMPS; tools/r06_corr_stamps.py): s_memrealtime (100 MHz) per workgroup at
-  // start / pipeline filled / f16 run done / fp8 run done / epilogue's stores drained, and where the workgroup ran (XCC_ID, HW_ID)
-#ifdef RUART_P8_STAMPS
-  // (per WAVE: [workgroup][wave][8])
-#define C8_STAMP(i) do { if (stamps && (threadIdx.x & 63) == 0) stamps[(blockIdx.x * 8 + (threadIdx.x >> 6)) * 8 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-  if (stamps && (threadIdx.x & 63) == 0) {
-    stamps[(blockIdx.x * 8 + (threadIdx.x >> 6)) * 8 + 6] = __builtin_amdgcn_s_getreg((20 /*HW_REG_XCC_ID*/) | (0 << 6) | (31 << 11));
-    stamps[(blockIdx.x * 8 + (threadIdx.x >> 6)) * 8 + 7] = __builtin_amdgcn_s_getreg((4 /*HW_REG_HW_ID*/) | (0 << 6) | (31 << 11));
-  }
-#else
-#define C8_STAMP(i)
-#endif
-  C8_STAMP(0);
+                                                            float* __restrict__ slabs, const CorrFold f) {
   constexpr int kHalf = 128 * CBKB;              // 16 KB half-tile
   constexpr int kOper = 2 * kHalf;               // 32 KB per operand K-tile
   constexpr int kBuf = 2 * kOper;                // 64 KB per K-tile
@@ -364,8 +308,8 @@ __global__ RUART_VGPR_ATTR __launch_bounds__(512, 2) void gemm_16c_nt_256p8(cons
       for (int j = 0; j < 4; ++j)
 #pragma unroll
         for (int i = 0; i < 2; ++i)
-          acc[hc * 2 + i][hr * 4 + j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wf[i], af[j], acc[hc * 2 + i][hr * 4 + j], RUART_C8_FMT,
-                                                                                         RUART_C8_FMT, 0, scale_w, 0, scale_a);
+          acc[hc * 2 + i][hr * 4 + j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wf[i], af[j], acc[hc * 2 + i][hr * 4 + j], 0 /* e4m3 */,
+                                                                                         0, 0, scale_w, 0, scale_a);
     } else {
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks)
@@ -389,10 +333,6 @@ __global__ RUART_VGPR_ATTR __launch_bounds__(512, 2) void gemm_16c_nt_256p8(cons
     __builtin_amdgcn_sched_barrier(0);
     read_a(D, 0);
     if (N1) stage_a(D ^ 1, 1, t + 1);
-#if RUART_P8_WAITS
-    // (this tile's W-h1, read one phase on, has landed; five younger half-tiles may be in flight - P8_VMCNT below)
-    if (N1) asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-#endif
     asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");     // the 4 W-h0 reads (issued first) are back: its slot may be restaged
     RUART_BAR();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -400,10 +340,6 @@ __global__ RUART_VGPR_ATTR __launch_bounds__(512, 2) void gemm_16c_nt_256p8(cons
     RUART_BAR();
     read_w(D, 1, wf1);
     if (N2) stage_w(D, 0, t + 2);
-#if RUART_P8_WAITS
-    // (this tile's A-h1 has landed)
-    if (N2) asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); else if (N1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
     RUART_BAR();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     quad(f8tag, 1, 0, wf1);
@@ -414,22 +350,12 @@ __global__ RUART_VGPR_ATTR __launch_bounds__(512, 2) void gemm_16c_nt_256p8(cons
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     quad(f8tag, 1, 1, wf1);
     RUART_BAR();
-#if RUART_P8_WAITS
-    // (K-tile t+1's W-h0 and A-h0 have landed)
-    if (N2) {
-      stage_w(D, 1, t + 2);
-      asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-    } else if (N1) {
-      asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    }
-#else
     if (N2) {
       stage_w(D, 1, t + 2);
       asm volatile("s_waitcnt vmcnt(6)" ::: "memory");     // K-tile t+1 complete; the 3 youngest half-tiles stay in flight
     } else if (N1) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
-#endif
     RUART_BAR();
     quad(f8tag, 0, 1, wf0);
     RUART_BAR();
@@ -438,13 +364,6 @@ __global__ RUART_VGPR_ATTR __launch_bounds__(512, 2) void gemm_16c_nt_256p8(cons
   using I1 = std::integral_constant<int, 1>;
   using Tt = std::true_type;
   using Ff = std::false_type;
-  // MFMA of the two runs.  Diagnostic builds (wrong numbers, right timing): RUART_ABL_MFMA 1 = the fp8 instruction in BOTH runs, 2 = the f16
-  // instruction in both - which of the run's properties makes an f16 K-tile 13 % longer than an fp8 K-tile
-#ifndef RUART_ABL_MFMA
-#define RUART_ABL_MFMA 0
-#endif
-  using FA = std::conditional_t<RUART_ABL_MFMA == 1, Tt, Ff>;
-  using FB = std::conditional_t<RUART_ABL_MFMA == 2, Ff, Tt>;
 
   // K-tiles [kb, ke) of this workgroup: everything, or slice `slice` of S (S even: a slice never straddles the f16 / fp8 boundary)
   int kb = 0, ke = NT;
@@ -460,16 +379,8 @@ __global__ RUART_VGPR_ATTR __launch_bounds__(512, 2) void gemm_16c_nt_256p8(cons
   stage_w(1, 0, kb + 1);
   stage_a(1, 0, kb + 1);
   stage_w(1, 1, kb + 1);
-#if RUART_P8_WAITS
-  asm volatile("s_waitcnt vmcnt(10)" ::: "memory");          // K-tile kb's W-h0 and A-h0 landed (this wave's share)
-#else
   asm volatile("s_waitcnt vmcnt(6)" ::: "memory");           // K-tile kb landed (this wave's share)
-#endif
   RUART_BAR();
-  C8_STAMP(1);
-#ifdef RUART_P8_STAMPS
-  const unsigned long long clk0 = __builtin_amdgcn_s_memtime();      // shader clock over the K loop (slot 5): cycles per K-tile, in-loop clock
-#endif
   if (wave >= 4) RUART_BAR();                                 // stagger: waves 4-7 run one barrier behind
   // The K loop as two optional runs - K-tiles [a0, a1) of the f16 phase, then [b0, b1) of the fp8 phase (each empty or an even count
   // >= 2): the whole product is (0, nt, nt, NT), a slice lives in one of the two, the no-correction ablation is (0, nt) alone.  The
@@ -484,30 +395,25 @@ __global__ RUART_VGPR_ATTR __launch_bounds__(512, 2) void gemm_16c_nt_256p8(cons
     int t = a0;
     const int body_end = a_last ? a1 - 2 : a1;
     for (; t < body_end; t += 2) {
-      tile(FA{}, I0{}, Tt{}, Tt{}, t);
-      tile(FA{}, I1{}, Tt{}, Tt{}, t + 1);
+      tile(Ff{}, I0{}, Tt{}, Tt{}, t);
+      tile(Ff{}, I1{}, Tt{}, Tt{}, t + 1);
     }
     if (a_last) {
-      tile(FA{}, I0{}, Tt{}, Ff{}, t);
-      tile(FA{}, I1{}, Ff{}, Ff{}, t + 1);
+      tile(Ff{}, I0{}, Tt{}, Ff{}, t);
+      tile(Ff{}, I1{}, Ff{}, Ff{}, t + 1);
     }
   }
-  C8_STAMP(2);
   if (b0 < b1) {
     int t = b0;
     for (; t + 2 < b1; t += 2) {
-      tile(FB{}, I0{}, Tt{}, Tt{}, t);
-      tile(FB{}, I1{}, Tt{}, Tt{}, t + 1);
+      tile(Tt{}, I0{}, Tt{}, Tt{}, t);
+      tile(Tt{}, I1{}, Tt{}, Tt{}, t + 1);
     }
-    tile(FB{}, I0{}, Tt{}, Ff{}, t);
-    tile(FB{}, I1{}, Ff{}, Ff{}, t + 1);
+    tile(Tt{}, I0{}, Tt{}, Ff{}, t);
+    tile(Tt{}, I1{}, Ff{}, Ff{}, t + 1);
   }
   if (wave < 4) RUART_BAR();                                  // waves 0-3 pair the lagging group's last barrier
   RUART_BAR();                                                // every wave is done reading operand tiles
-  C8_STAMP(3);
-#ifdef RUART_P8_STAMPS
-  if (stamps && (threadIdx.x & 63) == 0) stamps[(blockIdx.x * 8 + (threadIdx.x >> 6)) * 8 + 5] = __builtin_amdgcn_s_memtime() - clk0;
-#endif
 
   if (slice >= 0) {
     // partial sums of this slice, thread-major ([i][j][tid] x 4 floats: 16-byte coalesced stores, read back the same way)
@@ -519,10 +425,6 @@ __global__ RUART_VGPR_ATTR __launch_bounds__(512, 2) void gemm_16c_nt_256p8(cons
     return;
   }
   corr_epilogue<EPI, FOLD>(acc, smem, m0, n0, bias, R, ldr, C, ldc, C8, N, 0, 4, f);
-#ifdef RUART_P8_STAMPS
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-  C8_STAMP(4);
 }
 
 // ---- 256 x 128 tiles, TWO resident workgroups per CU ("dual" form; round 6) -----------------------------------------------------------
@@ -547,43 +449,11 @@ __global__ RUART_VGPR_ATTR __launch_bounds__(512, 2) void gemm_16c_nt_256p8(cons
 //     >= 3 phases to land, as the big kernel's single wait does.
 // EPI 0 / 2 (QKV, intermediate dense; FOLD or not), both correction products, no tail split.  M % 256 == 0, N % 128 == 0, K % 128 == 0.
 #define DBN 128
-// diagnostic builds: RUART_D_PRIO 0 = s_setprio 1 around every quadrant's MFMAs (as the 256 x 256 kernel), 1 = no priority changes, 2 = static
-// priority by seat; RUART_D_BAR2 1 = a second barrier behind every quadrant (the 256 x 256 kernel's phase shape)
-#ifndef RUART_D_PRIO
-#define RUART_D_PRIO 0
-#endif
-#ifndef RUART_D_BAR2
-#define RUART_D_BAR2 0
-#endif
-#if RUART_D_BAR2
-#define D_BAR2() RUART_BAR()
-#else
-#define D_BAR2()
-#endif
 template <int EPI, bool FOLD = false>
 __global__ __launch_bounds__(256, 2) void gemm_16c_nt_256x128d(const char* __restrict__ A16, const char* __restrict__ A8, int pitch_a,
                                                                const char* __restrict__ W16, const char* __restrict__ W8, int pitch_w,
                                                                const float* __restrict__ bias, void* __restrict__ C, int ldc,
-                                                               unsigned char* __restrict__ C8, int M, int N, int K, int order, const CorrFold f
-#ifdef RUART_P8_STAMPS
-                                                               , unsigned long long* __restrict__ stamps
-#endif
-) {
-#ifdef RUART_P8_STAMPS
-#define D8_STAMP(i) do { if (stamps && (threadIdx.x & 63) == 0) stamps[(blockIdx.x * 4 + (threadIdx.x >> 6)) * 8 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-  if (stamps && (threadIdx.x & 63) == 0) {
-    stamps[(blockIdx.x * 4 + (threadIdx.x >> 6)) * 8 + 6] = __builtin_amdgcn_s_getreg((20 /*HW_REG_XCC_ID*/) | (0 << 6) | (31 << 11));
-    stamps[(blockIdx.x * 4 + (threadIdx.x >> 6)) * 8 + 7] = __builtin_amdgcn_s_getreg((4 /*HW_REG_HW_ID*/) | (0 << 6) | (31 << 11));
-  }
-#else
-#define D8_STAMP(i)
-#endif
-  D8_STAMP(0);
-#if RUART_D_PRIO == 2
-  // static priority by SEAT (the wave slot on its SIMD: the two workgroups of a CU sit on different slots): one workgroup of the CU always
-  // takes the matrix pipe first, the other fills its gaps
-  if (__builtin_amdgcn_s_getreg((4 /*HW_REG_HW_ID*/) | (0 << 6) | (3 << 11)) & 1) __builtin_amdgcn_s_setprio(1);
-#endif
+                                                               unsigned char* __restrict__ C8, int M, int N, int K, int order, const CorrFold f) {
   constexpr int kHalfA = 128 * CBKB;             // 16 KB
   constexpr int kHalfW = 64 * CBKB;              // 8 KB
   constexpr int kWOff = 3 * kHalfA;              // the W slots [D][h] behind the A ring
@@ -648,16 +518,14 @@ __global__ __launch_bounds__(256, 2) void gemm_16c_nt_256x128d(const char* __res
   const int scale_w = 0x01010101 * (127 - RUART_C8_SHIFT), scale_a = 0x7f7f7f7f;
   auto quad = [&](auto f8tag, int hc, int hr, i32x8_t (&wf)[2]) {
     constexpr bool F8 = decltype(f8tag)::value;
-#if RUART_D_PRIO == 0
     __builtin_amdgcn_s_setprio(1);
-#endif
     if constexpr (F8) {
 #pragma unroll
       for (int j = 0; j < 4; ++j)
 #pragma unroll
         for (int i = 0; i < 2; ++i)
-          acc[hc * 2 + i][hr * 4 + j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wf[i], af[j], acc[hc * 2 + i][hr * 4 + j], RUART_C8_FMT,
-                                                                                         RUART_C8_FMT, 0, scale_w, 0, scale_a);
+          acc[hc * 2 + i][hr * 4 + j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wf[i], af[j], acc[hc * 2 + i][hr * 4 + j], 0 /* e4m3 */,
+                                                                                         0, 0, scale_w, 0, scale_a);
     } else {
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks)
@@ -671,9 +539,7 @@ __global__ __launch_bounds__(256, 2) void gemm_16c_nt_256x128d(const char* __res
                                                                                   acc[hc * 2 + i][hr * 4 + j], 0, 0, 0);
           }
     }
-#if RUART_D_PRIO == 0
     __builtin_amdgcn_s_setprio(0);
-#endif
   };
   int rd = 0;                                     // ring slot of the A half read next (half s -> slot s % 3); the half staged next goes to rd - 1
   auto ring_next = [](int s) { return s == 2 ? 0 : s + 1; };
@@ -689,7 +555,6 @@ __global__ __launch_bounds__(256, 2) void gemm_16c_nt_256x128d(const char* __res
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     RUART_BAR();
     quad(f8tag, 0, 0, wf0);
-    D_BAR2();
     // p1
     read_w(D, 1, wf1);
     if (N2) stage_w(D, 0, t + 2);
@@ -699,7 +564,6 @@ __global__ __launch_bounds__(256, 2) void gemm_16c_nt_256x128d(const char* __res
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     RUART_BAR();
     quad(f8tag, 1, 0, wf1);
-    D_BAR2();
     // p2
     rd = ring_next(rd);
     read_a(rd);
@@ -707,7 +571,6 @@ __global__ __launch_bounds__(256, 2) void gemm_16c_nt_256x128d(const char* __res
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     RUART_BAR();
     quad(f8tag, 1, 1, wf1);
-    D_BAR2();
     // p3
     if (N2) {
       stage_w(D, 1, t + 2);
@@ -717,7 +580,6 @@ __global__ __launch_bounds__(256, 2) void gemm_16c_nt_256x128d(const char* __res
     }
     RUART_BAR();
     quad(f8tag, 0, 1, wf0);
-    D_BAR2();
     rd = ring_next(rd);
   };
   using I0 = std::integral_constant<int, 0>;
@@ -733,15 +595,10 @@ __global__ __launch_bounds__(256, 2) void gemm_16c_nt_256x128d(const char* __res
   stage_w(1, 1, 1);
   asm volatile("s_waitcnt vmcnt(8)" ::: "memory");             // K-tile 0's W-h0, A-h0, W-h1 landed (this wave's share)
   RUART_BAR();
-  D8_STAMP(1);
-#ifdef RUART_P8_STAMPS
-  const unsigned long long clk0 = __builtin_amdgcn_s_memtime();
-#endif
   for (int t = 0; t < nt; t += 2) {                            // the f16 run (the fp8 run follows: every tile prefetches)
     tile(Ff{}, I0{}, Tt{}, Tt{}, t);
     tile(Ff{}, I1{}, Tt{}, Tt{}, t + 1);
   }
-  D8_STAMP(2);
   {
     int t = nt;
     for (; t + 2 < NT; t += 2) {
@@ -752,15 +609,7 @@ __global__ __launch_bounds__(256, 2) void gemm_16c_nt_256x128d(const char* __res
     tile(Tt{}, I1{}, Ff{}, Ff{}, t + 1);
   }
   RUART_BAR();                                                 // every wave is done reading operand tiles
-  D8_STAMP(3);
-#ifdef RUART_P8_STAMPS
-  if (stamps && (threadIdx.x & 63) == 0) stamps[(blockIdx.x * 4 + (threadIdx.x >> 6)) * 8 + 5] = __builtin_amdgcn_s_memtime() - clk0;
-#endif
   corr_epilogue<EPI, FOLD, 2>(acc, smem, m0, n0, bias, nullptr, 0, C, ldc, C8, N, 0, 4, f, FOLD ? &row_stat : nullptr);
-#ifdef RUART_P8_STAMPS
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-  D8_STAMP(4);
 }
 
 // Second launch of a tail-split product: tile n_full + blockIdx.x = the sum of its S slices IN SLICE ORDER (deterministic), then the
@@ -816,9 +665,6 @@ static inline bool corr_spans_ok(int M, int ldc, int ldr) {
   return (size_t)M * (size_t)ldc * 4 < ((size_t)1 << 32) && (size_t)M * (size_t)ldr * 4 < ((size_t)1 << 32);
 }
 extern int g_tile_order, g_tile_order_auto;
-#ifdef RUART_P8_STAMPS
-extern unsigned long long* g_p8_stamps;
-#endif
 // GROUP_M of the tile walk: ruart_tile_group_m (gemm_shared.h) unless ruart_gemm_set_tile_order pinned a value.  L2-miss traffic moves the
 // OTHER way (smallest at GROUP_M 2-3, profiles/r03_gemm_order_sweep_fetch.log): it is not what bounds this kernel.
 static inline int corr_tile_order(int M, int N, int K) {
@@ -878,11 +724,7 @@ static void launch_corr(const void* A16, const void* A8, int lda, const void* W1
   (void)done;
   hipLaunchKernelGGL(kern, dim3(p.n_full + p.r * p.S), dim3(512), lds, s, (const char*)A16, (const char*)A8, 2 * lda, (const char*)W16,
                      (const char*)W8, 2 * ldw, bias, residual, ldr, C, ldc, (unsigned char*)C8, M, N, K, order, n8, o8, p.n_full, p.S,
-                     (float*)tail_ws, fold
-#ifdef RUART_P8_STAMPS
-                     , g_p8_stamps
-#endif
-                     );
+                     (float*)tail_ws, fold);
   if (p.r > 0) {
     constexpr int flds = 8 * 32 * 272;                    // the epilogue's staging image
     auto fix = gemm_16c_fixup<EPI>;
@@ -911,11 +753,7 @@ static void launch_corr_dual(const void* A16, const void* A8, int lda, const voi
   static bool done = (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds), true);
   (void)done;
   hipLaunchKernelGGL(kern, dim3((M / CBM) * (N / DBN)), dim3(256), lds, s, (const char*)A16, (const char*)A8, 2 * lda, (const char*)W16,
-                     (const char*)W8, 2 * ldw, bias, C, ldc, (unsigned char*)C8, M, N, K, order, fold
-#ifdef RUART_P8_STAMPS
-                     , g_p8_stamps
-#endif
-                     );
+                     (const char*)W8, 2 * ldw, bias, C, ldc, (unsigned char*)C8, M, N, K, order, fold);
 }
 
 // ruart_gemm_16c_nt_sel with the tail split (above): tail_ws = ruart_gemm_16c_tail_ws_bytes(M, N, K, cus) bytes of scratch the call

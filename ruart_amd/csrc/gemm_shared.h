@@ -83,17 +83,9 @@ typedef __attribute__((address_space(3))) void* lptr_t;
 // that includes this header is re-established after the statement instead of silently reading ours.
 // Precondition: `base_uniform` and `lds_dst_uniform` are wave-uniform (the "s" constraint would otherwise insert a readfirstlane
 // and quietly use lane 0's value for every lane).
-// RUART_DMA_BUILTIN=1 (diagnostic builds) goes back to the builtin.
-#ifndef RUART_DMA_BUILTIN
-#define RUART_DMA_BUILTIN 0
-#endif
 __device__ __forceinline__ void dma16(const void* base_uniform, unsigned lane_byte_off, char* lds_dst_uniform) {
-#if RUART_DMA_BUILTIN
-  __builtin_amdgcn_global_load_lds((gptr_t)(reinterpret_cast<const char*>(base_uniform) + lane_byte_off), (lptr_t)lds_dst_uniform, 16, 0, 0);
-#else
   const unsigned lds_addr = (unsigned)(size_t)(lptr_t)lds_dst_uniform;
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds_addr), "v"(lane_byte_off), "s"(base_uniform) : "memory", "m0");
-#endif
 }
 
 #define RUART_BAR()                          \

@@ -95,13 +95,7 @@ __global__ __launch_bounds__(512, 2) void gemm_16_tn_256p8(const T16* __restrict
   for (int i = 0; i < 4; ++i)
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-#ifndef RUART_TN_ABLATE
-#define RUART_TN_ABLATE 0
-#endif
-  // diagnostic builds only (tools/build_variant.sh NAME -DRUART_TN_ABLATE=n): 1 no prefetch in the loop, 2 no fragment reads after the first
-  // K-tile, 4 no stagger.  0 in production.  (Issuing a phase's prefetch BEFORE its fragment reads was measured 30 % slower: the reads'
-  // issue is the critical path of the segment.)
-  constexpr int ab = RUART_TN_ABLATE;
+  // Issuing a phase's prefetch BEFORE its fragment reads was measured 30 % slower: the reads' issue is the critical path of the segment.
   const int fr = lane & 15, fq = lane >> 4;
   typedef typename Vec8<T16>::type frag_t;
   frag_t af[4][2], wfa[2][2], wfb[2][2];
@@ -147,26 +141,24 @@ __global__ __launch_bounds__(512, 2) void gemm_16_tn_256p8(const T16* __restrict
   auto tile = [&](auto dtag, auto n1tag, auto n2tag, int t) {
     constexpr int D = decltype(dtag)::value;
     constexpr bool N1 = decltype(n1tag)::value, N2 = decltype(n2tag)::value;
-    constexpr bool S1 = N1 && !(ab & 1), S2 = N2 && !(ab & 1);
-    const bool rd = !(ab & 2) || t == 0;
     auto run = [&](frag_t (&wc)[2][2], frag_t (&wn)[2][2]) {
       // phase 0: quadrant (rows h0, cols h0) - Q-h0 fragments already in wc; prefetch (t+1, P-h1)
-      if (rd) read_a(D, 0, 0, 4);
-      if (S1) stage_a(D ^ 1, 1, t + 1);
+      read_a(D, 0, 0, 4);
+      if (N1) stage_a(D ^ 1, 1, t + 1);
       RUART_BAR();
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       quad(0, 0, wc);
       RUART_BAR();
       // phase 1: (rows h0, cols h1); prefetch (t+2, Q-h0)
-      if (rd) read_w(D, 1, wn);
-      if (S2) stage_w(D, 0, t + 2);
+      read_w(D, 1, wn);
+      if (N2) stage_w(D, 0, t + 2);
       RUART_BAR();
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       quad(1, 0, wn);
       RUART_BAR();
       // phase 2: (rows h1, cols h1); prefetch (t+2, P-h0)
-      if (rd) read_a(D, 1, 0, 4);
-      if (S2) stage_a(D, 0, t + 2);
+      read_a(D, 1, 0, 4);
+      if (N2) stage_a(D, 0, t + 2);
       RUART_BAR();
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       quad(1, 1, wn);
@@ -178,13 +170,13 @@ __global__ __launch_bounds__(512, 2) void gemm_16_tn_256p8(const T16* __restrict
       RUART_BAR();
       // phase 3: (rows h1, cols h0) - operands in registers; prefetch (t+2, Q-h1); read (t+1, Q-h0) for the next tile's phase 0
       if (N2) {
-        if (S2) stage_w(D, 1, t + 2);
+        stage_w(D, 1, t + 2);
         asm volatile("s_waitcnt vmcnt(6)" ::: "memory");     // K-tile t+1 complete; the 3 youngest half-tiles stay in flight
       } else if (N1) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
       RUART_BAR();
-      if (N1 && rd) read_w(D ^ 1, 0, wn);
+      if (N1) read_w(D ^ 1, 0, wn);
       quad(0, 1, wc);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // (free: issued 16 MFMAs ago) the Q-h0 slot is restaged two barriers on
       RUART_BAR();
@@ -207,7 +199,7 @@ __global__ __launch_bounds__(512, 2) void gemm_16_tn_256p8(const T16* __restrict
   asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
   RUART_BAR();
   read_w(0, 0, wfa);
-  if (wave >= 4 && !(ab & 4)) RUART_BAR();       // stagger: waves 4-7 run one barrier behind
+  if (wave >= 4) RUART_BAR();       // stagger: waves 4-7 run one barrier behind
   int t = 0;
   for (; t + 2 < nt; t += 2) {
     tile(I0{}, Tt{}, Tt{}, t);
@@ -215,7 +207,7 @@ __global__ __launch_bounds__(512, 2) void gemm_16_tn_256p8(const T16* __restrict
   }
   tile(I0{}, Tt{}, Ff{}, t);
   tile(I1{}, Ff{}, Ff{}, t + 1);
-  if (wave < 4 && !(ab & 4)) RUART_BAR();
+  if (wave < 4) RUART_BAR();
   RUART_BAR();
 
   // accumulators -> LDS [m][n] per wave -> 16-byte fp32 stores

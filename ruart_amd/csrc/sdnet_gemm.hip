@@ -259,10 +259,6 @@ __device__ __forceinline__ void x3_tile(const float* __restrict__ A, long sam, l
   int moa[4] = {0, 0, 0, 0}, mob[4] = {0, 0, 0, 0};
   if (MSK == 1 && AMODE == 0) Stager<TM, AMODE, VWA, true>::mask_rows(moa, m0, M, K, tid, rpm);
   if (MSK == 2 && BMODE == 0) Stager<TM, BMODE, VWB, true>::mask_rows(mob, n0, N, K, tid, rpm);
-#ifndef RUART_X3_PF
-#define RUART_X3_PF 2
-#endif
-#if RUART_X3_PF == 2
   // Register-staged prefetch TWO K steps deep on the 128 tile (round 4): the trunk's products are short (K = 250 .. 1 800: 8-57 steps of
   // 32) and a step's MFMA work (~0.4 us at two workgroups per CU) is shorter than an L2 round trip, so with one step of lookahead every
   // store waited for its own loads (PMC: waves parked in s_waitcnt / s_barrier 45 % of their cycles).  Two register sets alternate with
@@ -316,9 +312,7 @@ __device__ __forceinline__ void x3_tile(const float* __restrict__ A, long sam, l
       __syncthreads();
       compute(st0);
     }
-  } else
-#endif
-  {
+  } else {
     Stager<TM, AMODE, VWA, MSK == 1> sa;
     Stager<TM, BMODE, VWB, MSK == 2> sb;
     if (kbeg < kend) {

@@ -181,9 +181,6 @@ __global__ __launch_bounds__(512) void lstm_bwd_kernel(const float* __restrict__
 // (issued at the top of the step, a whole step ago) and only then issues its own stores - otherwise the wait for the loads would
 // also drain the stores (a write latency per step: measured, 1.1 us).
 // ---------------------------------------------------------------------------------------------------------
-#ifndef RUART_LSTM_ABL
-#define RUART_LSTM_ABL 0       // diagnostic builds: 1 no x loads in the loop, 2 no global stores, 4 no gate transcendental, 8 no MFMAs
-#endif
 #define LRB 16                 // batch rows per workgroup
 #define LHS 272                // forward h image: 128 bf16 per row + 16 bytes pad
 #define LDS_DA 1040            // backward da image: 512 bf16 per row + 16 bytes pad
@@ -265,7 +262,7 @@ __global__ __launch_bounds__(512) void lstm_fwd_mfma_kernel(const float* __restr
   int cur = 0;
   for (int s = 0; s < T; ++s, cur ^= 1) {
     xp += sx;
-    if (s + 1 < T && !(RUART_LSTM_ABL & 1)) load_x(xp, xnext);
+    if (s + 1 < T) load_x(xp, xnext);
     bf16x8_t hh[4], hl[4];
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
@@ -275,39 +272,28 @@ __global__ __launch_bounds__(512) void lstm_fwd_mfma_kernel(const float* __restr
     f32x4_t acc[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) acc[i] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-    if (!(RUART_LSTM_ABL & 8)) {
-      // (consecutive MFMAs never touch the same accumulator: a dependent pair stalls for the matrix pipe's latency)
+    // (consecutive MFMAs never touch the same accumulator: a dependent pair stalls for the matrix pipe's latency)
 #pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
+    for (int ks = 0; ks < 4; ++ks) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) acc[i] = mfma_16x16x32(wl[i][ks], hh[ks], acc[i]);       // small terms first
+      for (int i = 0; i < 4; ++i) acc[i] = mfma_16x16x32(wl[i][ks], hh[ks], acc[i]);       // small terms first
 #pragma unroll
-        for (int i = 0; i < 4; ++i) acc[i] = mfma_16x16x32(wh[i][ks], hl[ks], acc[i]);
-      }
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) acc[i] = mfma_16x16x32(wh[i][ks], hh[ks], acc[i]);
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) acc[i][0] = (float)hh[i][0] + (float)hl[i][1] + (float)wh[i][0][0];
+      for (int i = 0; i < 4; ++i) acc[i] = mfma_16x16x32(wh[i][ks], hl[ks], acc[i]);
     }
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) acc[i] = mfma_16x16x32(wh[i][ks], hh[ks], acc[i]);
     // lane-local cell update of units u0 + r, batch row b
     f32x4_t ga[4], hv, cv, hpv;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const float pi = acc[0][r] + xcur[0][r], pf = acc[1][r] + xcur[1][r], pg = acc[2][r] + xcur[2][r], po = acc[3][r] + xcur[3][r];
-#if RUART_LSTM_ABL & 4
-      const float ig = pi * 0.1f, fg = pf * 0.1f, gg = pg * 0.1f, og = po * 0.1f;
-      c[r] = fg * c[r] + ig * gg;
-      const float tc = c[r];
-#else
       // sigmoid(x) = rcp(1 + exp2(-x log2 e)), tanh(x) = 2 sigmoid(2x) - 1 on the raw v_exp_f32 / v_rcp_f32 (1 ulp each): the IEEE
       // divide of 1.0f / (...) is a ten-instruction sequence
       const float ig = sigm_(pi), fg = sigm_(pf), gg = tanh_(pg), og = sigm_(po);
       c[r] = fg * c[r] + ig * gg;
       const float tc = tanh_(c[r]);
-#endif
       const float hn = og * tc;
       ga[0][r] = ig; ga[1][r] = fg; ga[2][r] = gg; ga[3][r] = og;
       hv[r] = hn;
@@ -333,14 +319,12 @@ __global__ __launch_bounds__(512) void lstm_fwd_mfma_kernel(const float* __restr
 #pragma unroll
     for (int i = 0; i < 4; ++i) xcur[i] = xnext[i];
     __builtin_amdgcn_sched_barrier(0);
-    if (!((RUART_LSTM_ABL & 2) && s + 1 < T)) {
-      *reinterpret_cast<f32x4_u*>(yp) = (f32x4_u){hv[0], hv[1], hv[2], hv[3]};
-      if (cp_) *reinterpret_cast<f32x4_u*>(cp_) = (f32x4_u){cv[0], cv[1], cv[2], cv[3]};
-      if (hpp) *reinterpret_cast<f32x4_u*>(hpp) = (f32x4_u){hpv[0], hpv[1], hpv[2], hpv[3]};
-      if (gp) {
+    *reinterpret_cast<f32x4_u*>(yp) = (f32x4_u){hv[0], hv[1], hv[2], hv[3]};
+    if (cp_) *reinterpret_cast<f32x4_u*>(cp_) = (f32x4_u){cv[0], cv[1], cv[2], cv[3]};
+    if (hpp) *reinterpret_cast<f32x4_u*>(hpp) = (f32x4_u){hpv[0], hpv[1], hpv[2], hpv[3]};
+    if (gp) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) *reinterpret_cast<f32x4_u*>(gp + (size_t)i * h) = (f32x4_u){ga[i][0], ga[i][1], ga[i][2], ga[i][3]};
-      }
+      for (int i = 0; i < 4; ++i) *reinterpret_cast<f32x4_u*>(gp + (size_t)i * h) = (f32x4_u){ga[i][0], ga[i][1], ga[i][2], ga[i][3]};
     }
     yp += sy;
     if (cp_) cp_ += sy;

@@ -174,7 +174,7 @@ def load(build_if_missing=True):
             raise OSError("libruart_hip.so not built: run `python -m ruart_amd.build`")
         from . import build as _build
         _build.build(verbose=False)
-    # RUART_HIP_LIB: load an experimental build of the same ABI instead (kernel A/B runs, tools/build_variant.sh)
+    # RUART_HIP_LIB: load an experimental build of the same ABI instead (kernel A/B runs)
     lib = ctypes.CDLL(os.environ.get("RUART_HIP_LIB") or LIB_PATH)
     for name, (res, args) in _SIGNATURES.items():
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch: fail loudly

@@ -1,9 +1,7 @@
 #!/usr/bin/env python3
 """The kind-3 product of the LayerNorm-folded encoder pass (ruart_gemm_16c_nt_fold: y = A W^T + b + LN(residual), written fp32 + split +
 row partials) alone on the device at the bench shapes, against the plain residual form (ruart_gemm_16c_nt) on the same operands.
-With RUART_HIP_LIB=build/libruart_hip_<variant>.so (tools/build_variant.sh nostats -DRUART_ABL_FOLD_NOSTATS / nosplit
--DRUART_ABL_FOLD_NOSPLIT): what the partial sums / the split copy cost the epilogue (valid inputs every launch - a whole-pass ablation
-feeds the next kernels garbage and their clock changes with it)."""
+RUART_HIP_LIB names another build of the library to measure (valid inputs every launch)."""
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Back-to-back launches of the fp16c QKV product for SECONDS seconds (power / clock sampling from outside: tools/r06_power.sh)."""
+"""Back-to-back launches of the fp16c QKV product for SECONDS seconds (power / clock sampling from outside)."""
 import os, sys, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ruart_amd import hip
