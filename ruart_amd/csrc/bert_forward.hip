@@ -13,47 +13,121 @@ extern "C" const char* ruart_version(void) { return "ruart_hip 0.1 gfx950"; }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 namespace {
+// Walks a workspace in 256-byte-aligned pieces.  With a null base it hands out null pointers and only counts: the layout functions below
+// are the ONE statement of each workspace, for the passes (real base) and for the size queries (null base) alike.
 struct Carve {
   char* base;
   size_t off;
-  void* take(size_t bytes) {
-    void* p = base + off;
+  template <typename T = void>
+  T* take(size_t bytes) {
+    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
     off += align_up(bytes, 256);
     return p;
   }
 };
+
+// `ruart_prof_real_rows` (the algorithmic row count of the GEMM launches in flight, gemm.hip) for the length of a pass: back to 0 on
+// every way out of it, the error returns included
+struct ProfRows {
+  explicit ProfRows(int n) { ruart_prof_real_rows = n; }
+  ~ProfRows() { ruart_prof_real_rows = 0; }
+};
 }  // namespace
 
-// RUART_DT_F16C ("f16 + fp8 correction", m->corr8 != 0; common.h): the residual stream, the layer outputs and the QKV rows are fp32;
-// every GEMM input exists as an f16 matrix plus a fp8 matrix of the same row pitch (two e4m3 bytes per element).
-static size_t corr_workspace_bytes(size_t R, size_t H, size_t I) {
-  size_t t = 0;
-  t += align_up(R * H * 4, 256);        // x32   embedding output (residual of layer 0)
-  t += 2 * align_up(R * H * 2, 256);    // x16, x8   current layer input as GEMM operand
-  t += align_up(R * 3 * H * 4, 256);    // qkv (fp32)
-  t += 2 * align_up(R * H * 2, 256);    // ctx16, ctx8
-  t += align_up(R * H * 4, 256);        // pre-LN rows (fp32)
-  t += align_up(R * H * 4, 256);        // mid32
-  t += 2 * align_up(R * H * 2, 256);    // mid16, mid8
-  t += 2 * align_up(R * I * 2, 256);    // ffn16, ffn8
-  return t;
-}
-
-// slabs of the GEMMs' tail split (gemm_corr.hip / gemm.hip): at most tail_cus slices of 256 x 256 fp32 per product, one product at a time
+// slabs of the GEMMs' tail split (gemm_shared.h): at most tail_cus slices of 256 x 256 fp32 per product, one product at a time
 static size_t tail_bytes(const ruart_bert_model* m) { return m->tail_cus > 0 ? (size_t)m->tail_cus * 256 * 256 * 4 : 0; }
 
-extern "C" size_t ruart_bert_workspace_bytes(const ruart_bert_model* m, int n_rows) {
+// Row partials of the folded passes (CorrFold, gemm_shared.h): four (sum, sumsq) slots = 32 bytes per row.  n_layers + 2 blocks are reserved
+// in both families, although the 16-bit folded pass has no use for partG (callers size their workspace by this).
+struct FoldParts {
+  float* partA;            // of y1, the layer in flight
+  float* partG;            // the gathered partials of the last layer's residual (fp16c pass, last-rows compaction)
+  float* partB;            // of y2: [n_layers][R][4][2] (R % 256 == 0: contiguous)
+  size_t partB_stride;     // floats between two layers of partB
+};
+static FoldParts fold_parts(Carve& c, size_t R, int n_layers) {
+  FoldParts f;
+  f.partA = c.take<float>(R * 32);
+  f.partG = c.take<float>(R * 32);
+  f.partB = c.take<float>((size_t)n_layers * align_up(R * 32, 256));
+  f.partB_stride = R * 8;
+  return f;
+}
+
+// The plain family (fp32 / bf16 / f16 storage): ruart_bert_forward and, `folded`, bert_forward_folded16.  The two passes share the
+// common part: the folded one keeps y1 in `mid` and does not read `pre`.
+struct PlainWs {
+  void *x0, *qkv, *ctx;    // embedding output; QKV rows; attention context
+  float* pre;              // pre-LayerNorm rows (fp32)
+  void *mid, *ffn;         // post-attention LayerNorm rows; FFN intermediate
+  void* tail;              // tail-split slabs (NULL without tail_cus; reserved for an fp32 model too, which never splits)
+  FoldParts part;          // `folded` only
+  size_t bytes;
+};
+static PlainWs plain_layout(const ruart_bert_model* m, int n_rows, bool folded, void* base) {
   const size_t es = m->dtype == RUART_DT_F32 ? 4 : 2;
   const size_t R = (size_t)n_rows, H = (size_t)m->hidden, I = (size_t)m->intermediate;
-  if (m->corr8) return corr_workspace_bytes(R, H, I) + align_up(tail_bytes(m), 256);
-  size_t t = align_up(tail_bytes(m), 256);   // (carved last)
-  t += align_up(R * H * es, 256);       // x0   embedding output
-  t += align_up(R * 3 * H * es, 256);   // qkv
-  t += align_up(R * H * es, 256);       // ctx
-  t += align_up(R * H * 4, 256);        // pre-LN rows (fp32)
-  t += align_up(R * H * es, 256);       // mid  (post-attention LN)
-  t += align_up(R * I * es, 256);       // ffn
-  return t;
+  Carve c{(char*)base, 0};
+  PlainWs w{};
+  w.x0 = c.take(R * H * es);
+  w.qkv = c.take(R * 3 * H * es);
+  w.ctx = c.take(R * H * es);
+  w.pre = c.take<float>(R * H * 4);
+  w.mid = c.take(R * H * es);
+  w.ffn = c.take(R * I * es);
+  w.tail = c.take(tail_bytes(m));
+  if (!tail_bytes(m)) w.tail = nullptr;
+  if (folded) w.part = fold_parts(c, R, m->n_layers);
+  w.bytes = c.off;
+  return w;
+}
+
+// The corr family - RUART_DT_F16C ("f16 + fp8 correction", m->corr8 != 0; common.h): the residual stream, the layer outputs and the QKV rows
+// are fp32; every GEMM input exists as an f16 matrix plus a fp8 matrix of the same row pitch (two e4m3 bytes per element).
+// bert_forward_corr and, `folded`, the fp16c branch of ruart_bert_forward_folded, which does not read `mid32` and never splits a tail: its
+// workspace carries the partials where the unfolded one carries the slabs.
+struct CorrWs {
+  float* x32;              // embedding output (residual of layer 0)
+  void *x16, *x8;          // current layer input as GEMM operand
+  float* qkv;
+  void *ctx16, *ctx8;
+  float *pre, *mid32;      // pre-LayerNorm rows; post-attention LayerNorm rows
+  void *mid16, *mid8, *ffn16, *ffn8;
+  void* tail;              // unfolded only: tail-split slabs (NULL without tail_cus)
+  FoldParts part;          // `folded` only
+  size_t bytes;
+};
+static CorrWs corr_layout(const ruart_bert_model* m, int n_rows, bool folded, void* base) {
+  const size_t R = (size_t)n_rows, H = (size_t)m->hidden, I = (size_t)m->intermediate;
+  Carve c{(char*)base, 0};
+  CorrWs w{};
+  w.x32 = c.take<float>(R * H * 4);
+  w.x16 = c.take(R * H * 2);
+  w.x8 = c.take(R * H * 2);
+  w.qkv = c.take<float>(R * 3 * H * 4);
+  w.ctx16 = c.take(R * H * 2);
+  w.ctx8 = c.take(R * H * 2);
+  w.pre = c.take<float>(R * H * 4);
+  w.mid32 = c.take<float>(R * H * 4);
+  w.mid16 = c.take(R * H * 2);
+  w.mid8 = c.take(R * H * 2);
+  w.ffn16 = c.take(R * I * 2);
+  w.ffn8 = c.take(R * I * 2);
+  if (folded) {
+    w.part = fold_parts(c, R, m->n_layers);
+  } else {
+    w.tail = c.take(tail_bytes(m));
+    if (!tail_bytes(m)) w.tail = nullptr;
+  }
+  w.bytes = c.off;
+  return w;
+}
+
+extern "C" size_t ruart_bert_workspace_bytes(const ruart_bert_model* m, int n_rows) {
+  return m->corr8 ? corr_layout(m, n_rows, false, nullptr).bytes : plain_layout(m, n_rows, false, nullptr).bytes;
+}
+extern "C" size_t ruart_bert_workspace_bytes_folded(const ruart_bert_model* m, int n_rows) {
+  return m->corr8 ? corr_layout(m, n_rows, true, nullptr).bytes : plain_layout(m, n_rows, true, nullptr).bytes;
 }
 
 // Which correction products each projection site carries (ruart_gemm_16c_nt_sel's `corr`: 3 = both - the default and the only setting
@@ -76,80 +150,147 @@ static int last_layer_rows(const ruart_bert_model* m, const ruart_bert_batch* b)
   return (b->n_last_rows > 0 && b->last_rows && b->n_last_rows < b->n_tokens && m->n_layers >= 2) ? b->n_last_rows : 0;
 }
 
+// What all four passes ask of a call.  Granularity of the rows and of the two widths: the passes that run on 256 x 256 tiles only (fp16c,
+// `folded`) want 256 throughout; the unfolded plain pass takes rows by 128 and widths by 128 (16-bit: the 128 x 128 kernel) or any
+// intermediate width and whole heads (fp32).  An fp16c model is f16 storage with the fp8 companions of its weights, and its attention
+// kernel has no long-block form.
+static bool pass_args_ok(const ruart_bert_model* m, const ruart_bert_batch* b, bool folded) {
+  const int H = m->hidden, I = m->intermediate, R = b->n_rows, dt = m->dtype;
+  if (dt != RUART_DT_F32 && dt != RUART_DT_BF16 && dt != RUART_DT_F16) return false;
+  struct Gran { int rows, hidden, inter; };
+  static const Gran kTile256{256, 256, 256};     // fp16c and folded passes: 256 x 256 tiles only
+  static const Gran kPlain16{128, 128, 128};     // unfolded bf16 / f16 pass: the 128 x 128 kernel takes what the 256 one does not
+  static const Gran kPlain32{128, 64, 1};        // unfolded fp32 pass: whole heads, any intermediate width
+  const Gran& g = (m->corr8 || folded) ? kTile256 : (dt == RUART_DT_F32 ? kPlain32 : kPlain16);
+  if (R <= 0 || R % g.rows || H % g.hidden || I % g.inter || b->n_tokens <= 0 || b->n_tokens > R || m->n_heads * 64 != H) return false;
+  if (m->corr8) {
+    if (dt != RUART_DT_F16 || b->n_long_blocks != 0 || b->n_blocks <= 0) return false;
+    if (!m->w8_qkv || !m->w8_ao || !m->w8_ff1 || !m->w8_ff2) return false;
+  }
+  return true;
+}
+
+// Last layer: only the rows some word span pools are needed from here on (ruart_bert_batch.last_rows).  Rows b->last_rows of up to three
+// row sets (context rows, residual rows; NULL src = unused) are compacted into buffers that are dead by now, and the rest of the layer
+// runs on *Rl = n_last rounded up to R's own granularity (the 256-row GEMM tile wants 256; n_last < n_tokens <= R, so *Rl <= R) rows,
+// leaving the last layer's output compacted.
+struct RowSet {
+  const void* src;
+  void* dst;
+  int row_bytes;
+};
+static int compact_last_rows(const ruart_bert_batch* b, int n_last, int R, RowSet s0, RowSet s1, RowSet s2, void* stream, int* Rl) {
+  const int gran = (R % 256) ? 128 : 256;
+  *Rl = (n_last + gran - 1) / gran * gran;
+  return ruart_rows_gather(b->last_rows, n_last, s0.src, s0.row_bytes, s0.dst, s0.row_bytes, s0.row_bytes, s1.src, s1.row_bytes, s1.dst,
+                           s1.row_bytes, s1.row_bytes, s2.src, s2.row_bytes, s2.dst, s2.row_bytes, s2.row_bytes, stream);
+}
+
 // The encoder in the f16 + fp8-correction mode.  layers_out: [n_layers][n_rows][hidden] fp32.
-static int bert_forward_corr(const ruart_bert_model* m, const ruart_bert_batch* b, void* layers_out, void* workspace, void* stream) {
+static int bert_forward_corr(const ruart_bert_model* m, const ruart_bert_batch* b, void* layers_out, const CorrWs& w, void* stream) {
   const int H = m->hidden, I = m->intermediate, R = b->n_rows;
-  if (R % 256 || H % 256 || I % 256 || b->n_long_blocks != 0 || b->n_blocks <= 0) return (int)hipErrorInvalidValue;
-  if (!m->w8_qkv || !m->w8_ao || !m->w8_ff1 || !m->w8_ff2) return (int)hipErrorInvalidValue;
-  Carve c{(char*)workspace, 0};
-  float* x32 = (float*)c.take((size_t)R * H * 4);
-  void* x16 = c.take((size_t)R * H * 2);
-  void* x8 = c.take((size_t)R * H * 2);
-  float* qkv = (float*)c.take((size_t)R * 3 * H * 4);
-  void* ctx16 = c.take((size_t)R * H * 2);
-  void* ctx8 = c.take((size_t)R * H * 2);
-  float* pre = (float*)c.take((size_t)R * H * 4);
-  float* mid32 = (float*)c.take((size_t)R * H * 4);
-  void* mid16 = c.take((size_t)R * H * 2);
-  void* mid8 = c.take((size_t)R * H * 2);
-  void* ffn16 = c.take((size_t)R * I * 2);
-  void* ffn8 = c.take((size_t)R * I * 2);
+  void* const tws = w.tail;
   const size_t tws_bytes = tail_bytes(m);
-  void* tws = tws_bytes ? c.take(tws_bytes) : nullptr;
   const int cus = m->tail_cus;
   // which projections take the tail split when tail_cus > 0: bit 0 QKV, 1 attention output, 2 FFN intermediate, 3 FFN output (experiments)
   static const int tail_sites = getenv("RUART_TAIL_SITES") ? atoi(getenv("RUART_TAIL_SITES")) : 15;
   const int cus_qkv = (tail_sites & 1) ? cus : 0, cus_ao = (tail_sites & 2) ? cus : 0, cus_ff1 = (tail_sites & 4) ? cus : 0,
             cus_ff2 = (tail_sites & 8) ? cus : 0;
-  int rc = ruart_bert_embed_ln_split(b->ids, b->pos_ids, m->word_emb, m->pos_emb, m->type_emb, m->emb_ln_g, m->emb_ln_b, m->ln_eps, x32,
-                                     x16, x8, H, R, H, stream);
+  int rc = ruart_bert_embed_ln_split(b->ids, b->pos_ids, m->word_emb, m->pos_emb, m->type_emb, m->emb_ln_g, m->emb_ln_b, m->ln_eps, w.x32,
+                                     w.x16, w.x8, H, R, H, stream);
   if (rc) return rc;
-  ruart_prof_real_rows = b->n_tokens;
-  const float* res = x32;
+  ProfRows prof(b->n_tokens);
+  const float* res = w.x32;
   const int n_last = last_layer_rows(m, b);
   for (int l = 0; l < m->n_layers; ++l) {
     float* out = (float*)layers_out + (size_t)l * R * H;
     const bool on = (g_corr_layers >> (l & 63)) & 1ull;
     const int c_qkv = on ? g_corr_site[0] : 0, c_ao = on ? g_corr_site[1] : 0, c_ff1 = on ? g_corr_site[2] : 0, c_ff2 = on ? g_corr_site[3] : 0;
-    if ((rc = ruart_gemm_16c_nt_ws(x16, x8, H, m->w_qkv[l], m->w8_qkv[l], H, m->b_qkv[l], nullptr, 0, qkv, 3 * H, nullptr, R, 3 * H, H,
+    if ((rc = ruart_gemm_16c_nt_ws(w.x16, w.x8, H, m->w_qkv[l], m->w8_qkv[l], H, m->b_qkv[l], nullptr, 0, w.qkv, 3 * H, nullptr, R, 3 * H, H,
                                    RUART_ACT_NONE, c_qkv, tws, tws_bytes, cus_qkv, stream)))
       return rc;
-    if ((rc = ruart_bert_attention_split(qkv, 3 * H, ctx16, ctx8, H, H, m->n_heads, b->n_blocks, b->blk_q0, b->blk_q1, b->blk_k0, b->blk_k1,
+    if ((rc = ruart_bert_attention_split(w.qkv, 3 * H, w.ctx16, w.ctx8, H, H, m->n_heads, b->n_blocks, b->blk_q0, b->blk_q1, b->blk_k0, b->blk_k1,
                                          b->tok_lo, b->tok_hi, b->key_bias, stream)))
       return rc;
-    // Last layer: only the rows some word span pools are needed from here on (ruart_bert_batch.last_rows).  Their context rows and
-    // residual rows are compacted into buffers that are dead by now - the layer's own GEMM operand x16 / x8 and the QKV rows - and the
-    // rest of the layer runs on Rl = ceil(n_last / 256) * 256 rows, leaving layers_out[last] compacted.
+    // last layer on the pooled rows only (compact_last_rows): context rows -> the layer's own GEMM operand x16 / x8, residual rows -> the
+    // QKV buffer, all dead by now
     int Rl = R;
-    const void *a16 = ctx16, *a8 = ctx8;
+    const void *a16 = w.ctx16, *a8 = w.ctx8;
     if (n_last > 0 && l == m->n_layers - 1) {
-      Rl = (n_last + 255) / 256 * 256;              // R is a multiple of 256 and n_last < n_tokens <= R: Rl <= R
-      if ((rc = ruart_rows_gather(b->last_rows, n_last, ctx16, (long long)H * 2, x16, (long long)H * 2, H * 2, ctx8, (long long)H * 2, x8,
-                                  (long long)H * 2, H * 2, res, (long long)H * 4, qkv, (long long)H * 4, H * 4, stream)))
-        return rc;
-      a16 = x16;
-      a8 = x8;
-      res = qkv;
+      if ((rc = compact_last_rows(b, n_last, R, {w.ctx16, w.x16, H * 2}, {w.ctx8, w.x8, H * 2}, {res, w.qkv, H * 4}, stream, &Rl))) return rc;
+      a16 = w.x16;
+      a8 = w.x8;
+      res = w.qkv;
       ruart_prof_real_rows = n_last;
     }
-    if ((rc = ruart_gemm_16c_nt_ws(a16, a8, H, m->w_ao[l], m->w8_ao[l], H, m->b_ao[l], res, H, pre, H, nullptr, Rl, H, H, RUART_ACT_NONE,
+    if ((rc = ruart_gemm_16c_nt_ws(a16, a8, H, m->w_ao[l], m->w8_ao[l], H, m->b_ao[l], res, H, w.pre, H, nullptr, Rl, H, H, RUART_ACT_NONE,
                                    c_ao, tws, tws_bytes, cus_ao, stream)))
       return rc;
-    if ((rc = ruart_rows_layernorm_split(pre, H, m->ln1_g[l], m->ln1_b[l], m->ln_eps, mid32, mid16, mid8, H, Rl, H, stream))) return rc;
-    if ((rc = ruart_gemm_16c_nt_ws(mid16, mid8, H, m->w_ff1[l], m->w8_ff1[l], H, m->b_ff1[l], nullptr, 0, ffn16, I, ffn8, Rl, I, H,
+    if ((rc = ruart_rows_layernorm_split(w.pre, H, m->ln1_g[l], m->ln1_b[l], m->ln_eps, w.mid32, w.mid16, w.mid8, H, Rl, H, stream))) return rc;
+    if ((rc = ruart_gemm_16c_nt_ws(w.mid16, w.mid8, H, m->w_ff1[l], m->w8_ff1[l], H, m->b_ff1[l], nullptr, 0, w.ffn16, I, w.ffn8, Rl, I, H,
                                    RUART_ACT_GELU, c_ff1, tws, tws_bytes, cus_ff1, stream)))
       return rc;
-    if ((rc = ruart_gemm_16c_nt_ws(ffn16, ffn8, I, m->w_ff2[l], m->w8_ff2[l], I, m->b_ff2[l], mid32, H, pre, H, nullptr, Rl, H, I,
+    if ((rc = ruart_gemm_16c_nt_ws(w.ffn16, w.ffn8, I, m->w_ff2[l], m->w8_ff2[l], I, m->b_ff2[l], w.mid32, H, w.pre, H, nullptr, Rl, H, I,
                                    RUART_ACT_NONE, c_ff2, tws, tws_bytes, cus_ff2, stream)))
       return rc;
     // (the last layer's GEMM-operand copies go to the dead context buffers: x16 / x8 may hold its compacted inputs)
-    if ((rc = ruart_rows_layernorm_split(pre, H, m->ln2_g[l], m->ln2_b[l], m->ln_eps, out, Rl == R ? x16 : ctx16, Rl == R ? x8 : ctx8, H, Rl, H,
-                                         stream)))
+    if ((rc = ruart_rows_layernorm_split(w.pre, H, m->ln2_g[l], m->ln2_b[l], m->ln_eps, out, Rl == R ? w.x16 : w.ctx16, Rl == R ? w.x8 : w.ctx8, H,
+                                         Rl, H, stream)))
       return rc;
     res = out;
   }
-  ruart_prof_real_rows = 0;
   return 0;
+}
+
+// ---- the plain 16-bit encoder (f16 / bf16 storage) with its LayerNorms folded into the projections around them (round 6; gemm.hip,
+// ruart_gemm_16_nt_fold) ---
+// layers_pre[l] = y2 of layer l, PRE-LayerNorm, in the model's 16-bit type; ln_stats[l][row] = (mu, rstd) taken from the unrounded fp32 y2.
+// Five launches per layer instead of seven: the two rows_layernorm passes (fp32 in, 16-bit out: 6 bytes per element each) are gone, the
+// attention-output / output dense write 2 bytes per element instead of 4.  Layer 0 reads the materialised embedding rows.  The last
+// layer is not compacted to the pooled rows (ruart_bert_batch.last_rows is refused: the sub-word pooling kernels read pre-LayerNorm rows
+// in fp32 only, so the training step keeps the unfolded 16-bit pass; this one serves whole-sequence encoding, bench.py --mode bert512).
+static int bert_forward_folded16(const ruart_bert_model* m, const ruart_bert_batch* b, void* layers_pre, float* ln_stats, const PlainWs& w,
+                                 void* stream) {
+  const int H = m->hidden, I = m->intermediate, R = b->n_rows, NL = m->n_layers, dt = m->dtype;
+  if (dt == RUART_DT_F32 || H > 1024) return (int)hipErrorInvalidValue;
+  if (last_layer_rows(m, b) > 0 || m->tail_cus > 0) return (int)hipErrorNotSupported;
+  const int np = H / 256;
+  const size_t es = 2;
+  const float eps = m->ln_eps;
+  int rc = ruart_bert_embed_ln(b->ids, b->pos_ids, m->word_emb, m->pos_emb, m->type_emb, m->emb_ln_g, m->emb_ln_b, eps, w.x0, H, dt, R, H, stream);
+  if (rc) return rc;
+  ProfRows prof(b->n_tokens);
+  const void* in = w.x0;                  // the layer's input rows: materialised (layer 0) or y2 of the layer before
+  const float* in_part = nullptr;
+  float* const partA = w.part.partA;
+  for (int l = 0; l < NL; ++l) {
+    void* out = (char*)layers_pre + (size_t)l * R * H * es;
+    float* pB = w.part.partB + (size_t)l * w.part.partB_stride;
+    if (l == 0)
+      rc = ruart_gemm_16_nt(in, H, m->w_qkv[l], H, m->b_qkv[l], nullptr, 0, dt, w.qkv, 3 * H, dt, R, 3 * H, H, RUART_ACT_NONE, dt, stream);
+    else
+      rc = ruart_gemm_16_nt_fold(in, H, m->w_qkv[l], H, m->b_qkv[l], 0, in_part, np, m->fold_c_qkv[l], m->fold_s_qkv[l], nullptr, 0, nullptr, 0,
+                                 nullptr, nullptr, w.qkv, 3 * H, nullptr, R, 3 * H, H, H, eps, dt, stream);
+    if (rc) return rc;
+    if ((rc = ruart_bert_attention(w.qkv, 3 * H, w.ctx, H, dt, H, m->n_heads, b->n_blocks, b->blk_q0, b->blk_q1, b->blk_k0, b->blk_k1, b->tok_lo,
+                                   b->tok_hi, b->key_bias, b->n_long_blocks, b->lblk_q0, b->lblk_q1, b->lblk_k0, b->lblk_k1, stream)))
+      return rc;
+    // y1 = ctx Wo^T + b + (layer 0: the embedding rows; else LN2_{l-1}(y2_{l-1})) -> mid, partA
+    if ((rc = ruart_gemm_16_nt_fold(w.ctx, H, m->w_ao[l], H, m->b_ao[l], 3, nullptr, 0, nullptr, 1.f, in, H, in_part, np, l ? m->ln2_g[l - 1] : nullptr,
+                                    l ? m->ln2_b[l - 1] : nullptr, w.mid, H, partA, R, H, H, H, eps, dt, stream)))
+      return rc;
+    // gelu(LN1_l(y1) W1^T + b1) -> ffn
+    if ((rc = ruart_gemm_16_nt_fold(w.mid, H, m->w_ff1[l], H, m->b_ff1[l], 2, partA, np, m->fold_c_ff1[l], m->fold_s_ff1[l], nullptr, 0, nullptr, 0,
+                                    nullptr, nullptr, w.ffn, I, nullptr, R, I, H, H, eps, dt, stream)))
+      return rc;
+    // y2 = ffn W2^T + b2 + LN1_l(y1) -> layers_pre[l], partB[l]
+    if ((rc = ruart_gemm_16_nt_fold(w.ffn, I, m->w_ff2[l], I, m->b_ff2[l], 3, nullptr, 0, nullptr, 1.f, w.mid, H, partA, np, m->ln1_g[l], m->ln1_b[l],
+                                    out, H, pB, R, H, I, H, eps, dt, stream)))
+      return rc;
+    in = out;
+    in_part = pB;
+  }
+  return ruart_rows_stats_finish(w.part.partB, np, NL * R, 1.0f / (float)H, eps, ln_stats, stream);
 }
 
 // ---- the fp16c encoder with its LayerNorms folded into the projections around them (gemm_corr.hip, CorrFold) -----------------------
@@ -158,240 +299,132 @@ static int bert_forward_corr(const ruart_bert_model* m, const ruart_bert_batch* 
 // LN1_l, GELU, split), output dense (kind 3: y2 = ffn W2^T + b + LN1_l(y1)).  Five launches per layer instead of seven; no launch reads
 // or writes a normalised row.  layers_pre[l] = y2 of layer l (PRE-LayerNorm), ln_stats[l][row] = (mu, rstd) of that row: the layer's
 // output is (y2 - mu) rstd gamma2_l + beta2_l, which ruart_bert_pool_mix_ln applies on the fly.
-static size_t fold_extra_bytes(size_t R, size_t H, int n_layers) {
-  (void)H;
-  return align_up(R * 32, 256) * ((size_t)n_layers + 2);      // partA, the gathered partials of the last layer's residual, partB per layer
-}
-extern "C" size_t ruart_bert_workspace_bytes_folded(const ruart_bert_model* m, int n_rows) {
-  if (!m->corr8)        // the plain 16-bit folded pass (bert_forward_folded16): the unfolded pass's carving + the row partials
-    return ruart_bert_workspace_bytes(m, n_rows) + fold_extra_bytes((size_t)n_rows, (size_t)m->hidden, m->n_layers);
-  return corr_workspace_bytes((size_t)n_rows, (size_t)m->hidden, (size_t)m->intermediate) + fold_extra_bytes((size_t)n_rows, (size_t)m->hidden, m->n_layers);
-}
-
-// ---- the plain 16-bit encoder (f16 / bf16 storage) with its LayerNorms folded the same way (round 6; gemm.hip, ruart_gemm_16_nt_fold) ---
-// layers_pre[l] = y2 of layer l, PRE-LayerNorm, in the model's 16-bit type; ln_stats[l][row] = (mu, rstd) taken from the unrounded fp32 y2.
-// Five launches per layer instead of seven: the two rows_layernorm passes (fp32 in, 16-bit out: 6 bytes per element each) are gone, the
-// attention-output / output dense write 2 bytes per element instead of 4.  Layer 0 reads the materialised embedding rows.  The last
-// layer is not compacted to the pooled rows (ruart_bert_batch.last_rows is refused: the sub-word pooling kernels read pre-LayerNorm rows
-// in fp32 only, so the training step keeps the unfolded 16-bit pass; this one serves whole-sequence encoding, bench.py --mode bert512).
-static int bert_forward_folded16(const ruart_bert_model* m, const ruart_bert_batch* b, void* layers_pre, float* ln_stats, void* workspace,
-                                 void* stream) {
-  const int H = m->hidden, I = m->intermediate, R = b->n_rows, NL = m->n_layers, dt = m->dtype;
-  if (dt != RUART_DT_F16 && dt != RUART_DT_BF16) return (int)hipErrorInvalidValue;
-  if (R <= 0 || R % 256 || H % 256 || I % 256 || H > 1024 || b->n_tokens > R || b->n_tokens <= 0 || m->n_heads * 64 != H) return (int)hipErrorInvalidValue;
-  if (last_layer_rows(m, b) > 0 || m->tail_cus > 0) return (int)hipErrorNotSupported;
-  const int np = H / 256;
-  const size_t es = 2;
-  Carve c{(char*)workspace, 0};
-  void* x0 = c.take((size_t)R * H * es);
-  void* qkv = c.take((size_t)R * 3 * H * es);
-  void* ctx = c.take((size_t)R * H * es);
-  c.take((size_t)R * H * 4);                           // (the unfolded pass's fp32 pre-LayerNorm rows: the two forms share one carving)
-  void* mid = c.take((size_t)R * H * es);              // y1, pre-LayerNorm
-  void* ffn = c.take((size_t)R * I * es);
-  float* partA = (float*)c.take((size_t)R * 32);
-  c.take((size_t)R * 32);
-  float* partB = (float*)c.take(0);                    // [n_layers][R][4][2]
-  const size_t partB_stride = (size_t)R * 8;
-  const float eps = m->ln_eps;
-  int rc = ruart_bert_embed_ln(b->ids, b->pos_ids, m->word_emb, m->pos_emb, m->type_emb, m->emb_ln_g, m->emb_ln_b, eps, x0, H, dt, R, H, stream);
-  if (rc) return rc;
-  ruart_prof_real_rows = b->n_tokens;
-  const void* in = x0;                    // the layer's input rows: materialised (layer 0) or y2 of the layer before
-  const float* in_part = nullptr;
-  for (int l = 0; l < NL; ++l) {
-    void* out = (char*)layers_pre + (size_t)l * R * H * es;
-    float* pB = partB + (size_t)l * partB_stride;
-    if (l == 0)
-      rc = ruart_gemm_16_nt(in, H, m->w_qkv[l], H, m->b_qkv[l], nullptr, 0, dt, qkv, 3 * H, dt, R, 3 * H, H, RUART_ACT_NONE, dt, stream);
-    else
-      rc = ruart_gemm_16_nt_fold(in, H, m->w_qkv[l], H, m->b_qkv[l], 0, in_part, np, m->fold_c_qkv[l], m->fold_s_qkv[l], nullptr, 0, nullptr, 0,
-                                 nullptr, nullptr, qkv, 3 * H, nullptr, R, 3 * H, H, H, eps, dt, stream);
-    if (rc) return rc;
-    if ((rc = ruart_bert_attention(qkv, 3 * H, ctx, H, dt, H, m->n_heads, b->n_blocks, b->blk_q0, b->blk_q1, b->blk_k0, b->blk_k1, b->tok_lo,
-                                   b->tok_hi, b->key_bias, b->n_long_blocks, b->lblk_q0, b->lblk_q1, b->lblk_k0, b->lblk_k1, stream)))
-      return rc;
-    // y1 = ctx Wo^T + b + (layer 0: the embedding rows; else LN2_{l-1}(y2_{l-1})) -> mid, partA
-    if ((rc = ruart_gemm_16_nt_fold(ctx, H, m->w_ao[l], H, m->b_ao[l], 3, nullptr, 0, nullptr, 1.f, in, H, in_part, np, l ? m->ln2_g[l - 1] : nullptr,
-                                    l ? m->ln2_b[l - 1] : nullptr, mid, H, partA, R, H, H, H, eps, dt, stream)))
-      return rc;
-    // gelu(LN1_l(y1) W1^T + b1) -> ffn
-    if ((rc = ruart_gemm_16_nt_fold(mid, H, m->w_ff1[l], H, m->b_ff1[l], 2, partA, np, m->fold_c_ff1[l], m->fold_s_ff1[l], nullptr, 0, nullptr, 0,
-                                    nullptr, nullptr, ffn, I, nullptr, R, I, H, H, eps, dt, stream)))
-      return rc;
-    // y2 = ffn W2^T + b2 + LN1_l(y1) -> layers_pre[l], partB[l]
-    if ((rc = ruart_gemm_16_nt_fold(ffn, I, m->w_ff2[l], I, m->b_ff2[l], 3, nullptr, 0, nullptr, 1.f, mid, H, partA, np, m->ln1_g[l], m->ln1_b[l],
-                                    out, H, pB, R, H, I, H, eps, dt, stream)))
-      return rc;
-    in = out;
-    in_part = pB;
-  }
-  ruart_prof_real_rows = 0;
-  return ruart_rows_stats_finish(partB, np, NL * R, 1.0f / (float)H, eps, ln_stats, stream);
-}
-
-
 extern "C" int ruart_bert_forward_folded(const ruart_bert_model* m, const ruart_bert_batch* b, void* layers_pre, float* ln_stats, void* workspace,
                                          size_t workspace_bytes, void* stream) {
   RUART_ENTRY();
   const int H = m->hidden, I = m->intermediate, R = b->n_rows, NL = m->n_layers;
   if (!m->ln_fold || !m->fold_c_qkv || !m->fold_c_ff1 || !m->fold_s_qkv || !m->fold_s_ff1 || !layers_pre || !ln_stats) return (int)hipErrorInvalidValue;
+  if (!pass_args_ok(m, b, true)) return (int)hipErrorInvalidValue;
   if (!m->corr8) {
-    if (workspace_bytes < ruart_bert_workspace_bytes_folded(m, R)) return (int)hipErrorInvalidValue;
-    return bert_forward_folded16(m, b, layers_pre, ln_stats, workspace, stream);
+    const PlainWs w16 = plain_layout(m, R, true, workspace);
+    if (workspace_bytes < w16.bytes) return (int)hipErrorInvalidValue;
+    return bert_forward_folded16(m, b, layers_pre, ln_stats, w16, stream);
   }
-  if (m->dtype != RUART_DT_F16) return (int)hipErrorInvalidValue;
-  if (R <= 0 || R % 256 || H % 256 || I % 256 || b->n_long_blocks != 0 || b->n_blocks <= 0 || b->n_tokens > R || b->n_tokens <= 0 ||
-      m->n_heads * 64 != H || !layers_pre || !ln_stats)
-    return (int)hipErrorInvalidValue;
-  if (!m->w8_qkv || !m->w8_ao || !m->w8_ff1 || !m->w8_ff2) return (int)hipErrorInvalidValue;
-  if (workspace_bytes < ruart_bert_workspace_bytes_folded(m, R)) return (int)hipErrorInvalidValue;
+  const CorrWs w = corr_layout(m, R, true, workspace);
+  if (workspace_bytes < w.bytes) return (int)hipErrorInvalidValue;
   // The folded pass always runs both correction products in every layer and never splits a tail: the ablation knobs of the unfolded
   // pass (ruart_bert_set_correction, ruart_bert_model.tail_cus) are refused here instead of being silently ignored (advisor, round 5)
   if (m->tail_cus > 0 || g_corr_layers != ~0ull || g_corr_site[0] != 3 || g_corr_site[1] != 3 || g_corr_site[2] != 3 || g_corr_site[3] != 3)
     return (int)hipErrorNotSupported;
   const int np = H / 256;
-  Carve c{(char*)workspace, 0};
-  float* x32 = (float*)c.take((size_t)R * H * 4);
-  void* x16 = c.take((size_t)R * H * 2);
-  void* x8 = c.take((size_t)R * H * 2);
-  float* qkv = (float*)c.take((size_t)R * 3 * H * 4);
-  void* ctx16 = c.take((size_t)R * H * 2);
-  void* ctx8 = c.take((size_t)R * H * 2);
-  float* pre = (float*)c.take((size_t)R * H * 4);
-  c.take((size_t)R * H * 4);                          // (the unfolded pass's mid32: the two forms share one carving of the common part)
-  void* mid16 = c.take((size_t)R * H * 2);
-  void* mid8 = c.take((size_t)R * H * 2);
-  void* ffn16 = c.take((size_t)R * I * 2);
-  void* ffn8 = c.take((size_t)R * I * 2);
-  float* partA = (float*)c.take((size_t)R * 32);       // row partials: four (sum, sumsq) slots per row, np of them used
-  float* partG = (float*)c.take((size_t)R * 32);
-  float* partB = (float*)c.take(0);                    // [n_layers][R][4][2] (R % 256 == 0: contiguous)
-  const size_t partB_stride = (size_t)R * 8;
+  float* const partA = w.part.partA;     // row partials: four (sum, sumsq) slots per row, np of them used
   hipStream_t s = (hipStream_t)stream;
   const float eps = m->ln_eps;
-  int rc = ruart_bert_embed_ln_split(b->ids, b->pos_ids, m->word_emb, m->pos_emb, m->type_emb, m->emb_ln_g, m->emb_ln_b, eps, x32, x16, x8, H, R,
-                                     H, stream);
+  int rc = ruart_bert_embed_ln_split(b->ids, b->pos_ids, m->word_emb, m->pos_emb, m->type_emb, m->emb_ln_g, m->emb_ln_b, eps, w.x32, w.x16, w.x8, H,
+                                     R, H, stream);
   if (rc) return rc;
-  ruart_prof_real_rows = b->n_tokens;
+  ProfRows prof(b->n_tokens);
   const int n_last = last_layer_rows(m, b);
-  const float* res = x32;                 // residual rows of the attention-output dense: materialised (layer 0) or y2 of the layer before
+  const float* res = w.x32;               // residual rows of the attention-output dense: materialised (layer 0) or y2 of the layer before
   const float* res_part = nullptr;
   for (int l = 0; l < NL; ++l) {
     float* out = (float*)layers_pre + (size_t)l * R * H;
-    float* pB = partB + (size_t)l * partB_stride;
-    const float* pPrev = l ? partB + (size_t)(l - 1) * partB_stride : nullptr;
-    if ((rc = ruart_gemm_16c_nt_fold(x16, x8, H, m->w_qkv[l], m->w8_qkv[l], H, m->b_qkv[l], 0, pPrev, np, l ? m->fold_c_qkv[l] : nullptr,
-                                     l ? m->fold_s_qkv[l] : 1.f, nullptr, 0, nullptr, 0, nullptr, nullptr, qkv, 3 * H, nullptr, nullptr, nullptr, R,
+    float* pB = w.part.partB + (size_t)l * w.part.partB_stride;
+    const float* pPrev = l ? w.part.partB + (size_t)(l - 1) * w.part.partB_stride : nullptr;
+    if ((rc = ruart_gemm_16c_nt_fold(w.x16, w.x8, H, m->w_qkv[l], m->w8_qkv[l], H, m->b_qkv[l], 0, pPrev, np, l ? m->fold_c_qkv[l] : nullptr,
+                                     l ? m->fold_s_qkv[l] : 1.f, nullptr, 0, nullptr, 0, nullptr, nullptr, w.qkv, 3 * H, nullptr, nullptr, nullptr, R,
                                      3 * H, H, H, eps, stream)))
       return rc;
-    if ((rc = ruart_bert_attention_split(qkv, 3 * H, ctx16, ctx8, H, H, m->n_heads, b->n_blocks, b->blk_q0, b->blk_q1, b->blk_k0, b->blk_k1,
+    if ((rc = ruart_bert_attention_split(w.qkv, 3 * H, w.ctx16, w.ctx8, H, H, m->n_heads, b->n_blocks, b->blk_q0, b->blk_q1, b->blk_k0, b->blk_k1,
                                          b->tok_lo, b->tok_hi, b->key_bias, stream)))
       return rc;
     int Rl = R;
-    const void *a16 = ctx16, *a8 = ctx8;
+    const void *a16 = w.ctx16, *a8 = w.ctx8;
     if (n_last > 0 && l == NL - 1) {
       // last layer on the pooled rows only (bert_forward_corr): context rows -> x16 / x8, residual rows (y2 of the layer before, raw) ->
       // the QKV buffer, their partials -> partG; the pad rows of the compacted residual are zeroed (their stale partials stay finite)
-      Rl = (n_last + 255) / 256 * 256;
-      if ((rc = ruart_rows_gather(b->last_rows, n_last, ctx16, (long long)H * 2, x16, (long long)H * 2, H * 2, ctx8, (long long)H * 2, x8,
-                                  (long long)H * 2, H * 2, res, (long long)H * 4, qkv, (long long)H * 4, H * 4, stream)))
+      if ((rc = compact_last_rows(b, n_last, R, {w.ctx16, w.x16, H * 2}, {w.ctx8, w.x8, H * 2}, {res, w.qkv, H * 4}, stream, &Rl))) return rc;
+      if ((rc = ruart_rows_gather(b->last_rows, n_last, res_part, 32, w.part.partG, 32, 32, nullptr, 0, nullptr, 0, 0, nullptr, 0, nullptr, 0, 0, stream)))
         return rc;
-      if ((rc = ruart_rows_gather(b->last_rows, n_last, res_part, 32, partG, 32, 32, nullptr, 0, nullptr, 0, 0, nullptr, 0, nullptr, 0, 0, stream)))
-        return rc;
-      if (Rl > n_last && hipMemsetAsync(qkv + (size_t)n_last * H, 0, (size_t)(Rl - n_last) * H * 4, s) != hipSuccess) return (int)hipGetLastError();
-      a16 = x16;
-      a8 = x8;
-      res = qkv;
-      res_part = partG;
+      if (Rl > n_last && hipMemsetAsync(w.qkv + (size_t)n_last * H, 0, (size_t)(Rl - n_last) * H * 4, s) != hipSuccess) return (int)hipGetLastError();
+      a16 = w.x16;
+      a8 = w.x8;
+      res = w.qkv;
+      res_part = w.part.partG;
       ruart_prof_real_rows = n_last;
     }
     // y1 -> pre (fp32), mid16 / mid8 (split), partA
     if ((rc = ruart_gemm_16c_nt_fold(a16, a8, H, m->w_ao[l], m->w8_ao[l], H, m->b_ao[l], 3, nullptr, 0, nullptr, 1.f, res, H, res_part, np,
-                                     l ? m->ln2_g[l - 1] : nullptr, l ? m->ln2_b[l - 1] : nullptr, pre, H, mid16, mid8, partA, Rl, H, H, H, eps,
+                                     l ? m->ln2_g[l - 1] : nullptr, l ? m->ln2_b[l - 1] : nullptr, w.pre, H, w.mid16, w.mid8, partA, Rl, H, H, H, eps,
                                      stream)))
       return rc;
-    if ((rc = ruart_gemm_16c_nt_fold(mid16, mid8, H, m->w_ff1[l], m->w8_ff1[l], H, m->b_ff1[l], 2, partA, np, m->fold_c_ff1[l], m->fold_s_ff1[l],
-                                     nullptr, 0, nullptr, 0, nullptr, nullptr, ffn16, I, nullptr, ffn8, nullptr, Rl, I, H, H, eps, stream)))
+    if ((rc = ruart_gemm_16c_nt_fold(w.mid16, w.mid8, H, m->w_ff1[l], m->w8_ff1[l], H, m->b_ff1[l], 2, partA, np, m->fold_c_ff1[l], m->fold_s_ff1[l],
+                                     nullptr, 0, nullptr, 0, nullptr, nullptr, w.ffn16, I, nullptr, w.ffn8, nullptr, Rl, I, H, H, eps, stream)))
       return rc;
     // y2 -> layers_pre[l] (fp32), the next layer's operand (split; the last layer's goes to the dead context buffers), partB[l]
-    if ((rc = ruart_gemm_16c_nt_fold(ffn16, ffn8, I, m->w_ff2[l], m->w8_ff2[l], I, m->b_ff2[l], 3, nullptr, 0, nullptr, 1.f, pre, H, partA, np,
-                                     m->ln1_g[l], m->ln1_b[l], out, H, Rl == R ? x16 : ctx16, Rl == R ? x8 : ctx8, pB, Rl, H, I, H, eps, stream)))
+    if ((rc = ruart_gemm_16c_nt_fold(w.ffn16, w.ffn8, I, m->w_ff2[l], m->w8_ff2[l], I, m->b_ff2[l], 3, nullptr, 0, nullptr, 1.f, w.pre, H, partA, np,
+                                     m->ln1_g[l], m->ln1_b[l], out, H, Rl == R ? w.x16 : w.ctx16, Rl == R ? w.x8 : w.ctx8, pB, Rl, H, I, H, eps, stream)))
       return rc;
     res = out;
     res_part = pB;
   }
-  ruart_prof_real_rows = 0;
   // (mu, rstd) of every layer's rows for the consumers of the layer outputs: one launch over [n_layers][R]
-  return ruart_rows_stats_finish(partB, np, NL * R, 1.0f / (float)H, eps, ln_stats, stream);
+  return ruart_rows_stats_finish(w.part.partB, np, NL * R, 1.0f / (float)H, eps, ln_stats, stream);
 }
 
 extern "C" int ruart_bert_forward(const ruart_bert_model* m, const ruart_bert_batch* b, void* layers_out, void* workspace,
                                   size_t workspace_bytes, void* stream) {
   RUART_ENTRY();
   if (m->ln_fold) return (int)hipErrorInvalidValue;       // this model's QKV / intermediate weights are the folded forms: ruart_bert_forward_folded
+  if (!pass_args_ok(m, b, false)) return (int)hipErrorInvalidValue;
   const int H = m->hidden, I = m->intermediate, R = b->n_rows, dt = m->dtype;
-  if (R % 128 || b->n_tokens > R || b->n_tokens <= 0 || H % 64 || m->n_heads * 64 != H) return (int)hipErrorInvalidValue;
-  if (dt != RUART_DT_F32 && (H % 128 || I % 128)) return (int)hipErrorInvalidValue;
-  if (dt != RUART_DT_F32 && dt != RUART_DT_BF16 && dt != RUART_DT_F16) return (int)hipErrorInvalidValue;
-  if (workspace_bytes < ruart_bert_workspace_bytes(m, R)) return (int)hipErrorInvalidValue;
   if (m->corr8) {
-    if (dt != RUART_DT_F16) return (int)hipErrorInvalidValue;
-    return bert_forward_corr(m, b, layers_out, workspace, stream);
+    const CorrWs wc = corr_layout(m, R, false, workspace);
+    if (workspace_bytes < wc.bytes) return (int)hipErrorInvalidValue;
+    return bert_forward_corr(m, b, layers_out, wc, stream);
   }
+  const PlainWs w = plain_layout(m, R, false, workspace);
+  if (workspace_bytes < w.bytes) return (int)hipErrorInvalidValue;
   const size_t es = dt == RUART_DT_F32 ? 4 : 2;
-  Carve c{(char*)workspace, 0};
-  void* x0 = c.take((size_t)R * H * es);
-  void* qkv = c.take((size_t)R * 3 * H * es);
-  void* ctx = c.take((size_t)R * H * es);
-  float* pre = (float*)c.take((size_t)R * H * 4);
-  void* mid = c.take((size_t)R * H * es);
-  void* ffn = c.take((size_t)R * I * es);
 
-  int rc = ruart_bert_embed_ln(b->ids, b->pos_ids, m->word_emb, m->pos_emb, m->type_emb, m->emb_ln_g, m->emb_ln_b, m->ln_eps, x0, H,
+  int rc = ruart_bert_embed_ln(b->ids, b->pos_ids, m->word_emb, m->pos_emb, m->type_emb, m->emb_ln_g, m->emb_ln_b, m->ln_eps, w.x0, H,
                                dt, R, H, stream);
   if (rc) return rc;
 
-  const size_t tws_bytes = dt != RUART_DT_F32 ? tail_bytes(m) : 0;
-  void* tws = tws_bytes ? c.take(tws_bytes) : nullptr;
+  const size_t tws_bytes = tail_bytes(m);
   auto gemm = [&](const void* A, int K, const void* W, const float* bias, const void* res, void* C, int out_dt, int N, int act, int rows) {
     if (dt != RUART_DT_F32)
-      return ruart_gemm_16_nt_ws(A, K, W, K, bias, res, N, dt, C, N, out_dt, rows, N, K, act, dt, tws, tws_bytes, m->tail_cus, stream);
+      return ruart_gemm_16_nt_ws(A, K, W, K, bias, res, N, dt, C, N, out_dt, rows, N, K, act, dt, w.tail, tws_bytes, m->tail_cus, stream);
     if (m->f32_gemm == 1)                                        // fp32 storage, split-bf16 products (no K split at these sizes)
       return ruart_gemm_x3((const float*)A, K, 1, (const float*)W, 1, K, bias, (const float*)res, N, act, (float*)C, N, rows, N, K,
                            nullptr, 0, nullptr, nullptr, 1.f, nullptr, 1, stream);
     return ruart_gemm_f32_nt((const float*)A, K, (const float*)W, K, bias, (const float*)res, N, (float*)C, N, rows, N, K, act, stream);
   };
 
-  ruart_prof_real_rows = b->n_tokens;
-  const void* in = x0;
+  ProfRows prof(b->n_tokens);
+  const void* in = w.x0;
   const int n_last = last_layer_rows(m, b);
   for (int l = 0; l < m->n_layers; ++l) {
     void* out = (char*)layers_out + (size_t)l * R * H * es;
-    if ((rc = gemm(in, H, m->w_qkv[l], m->b_qkv[l], nullptr, qkv, dt, 3 * H, RUART_ACT_NONE, R))) return rc;
-    if ((rc = ruart_bert_attention(qkv, 3 * H, ctx, H, dt, H, m->n_heads, b->n_blocks, b->blk_q0, b->blk_q1, b->blk_k0, b->blk_k1,
+    if ((rc = gemm(in, H, m->w_qkv[l], m->b_qkv[l], nullptr, w.qkv, dt, 3 * H, RUART_ACT_NONE, R))) return rc;
+    if ((rc = ruart_bert_attention(w.qkv, 3 * H, w.ctx, H, dt, H, m->n_heads, b->n_blocks, b->blk_q0, b->blk_q1, b->blk_k0, b->blk_k1,
                                    b->tok_lo, b->tok_hi, b->key_bias, b->n_long_blocks, b->lblk_q0, b->lblk_q1, b->lblk_k0, b->lblk_k1, stream)))
       return rc;
-    // last layer on the pooled rows only (see bert_forward_corr): context -> x0 (dead since layer 0), residual -> the QKV buffer
+    // last layer on the pooled rows only (compact_last_rows): context -> x0 (dead since layer 0), residual -> the QKV buffer
     int Rl = R;
-    const void *a = ctx, *res = in;
+    const void *a = w.ctx, *res = in;
     if (n_last > 0 && l == m->n_layers - 1) {
-      const int gran = (R % 256) ? 128 : 256;      // R's own granularity (the 256-row GEMM tile wants 256): n_last < n_tokens <= R, so Rl <= R
-      Rl = (n_last + gran - 1) / gran * gran;
-      if ((rc = ruart_rows_gather(b->last_rows, n_last, ctx, (long long)H * es, x0, (long long)H * es, (int)(H * es), in, (long long)H * es, qkv,
-                                  (long long)H * es, (int)(H * es), nullptr, 0, nullptr, 0, 0, stream)))
-        return rc;
-      a = x0;
-      res = qkv;
+      if ((rc = compact_last_rows(b, n_last, R, {w.ctx, w.x0, (int)(H * es)}, {in, w.qkv, (int)(H * es)}, {nullptr, nullptr, 0}, stream, &Rl))) return rc;
+      a = w.x0;
+      res = w.qkv;
       ruart_prof_real_rows = n_last;
     }
-    if ((rc = gemm(a, H, m->w_ao[l], m->b_ao[l], res, pre, RUART_DT_F32, H, RUART_ACT_NONE, Rl))) return rc;
-    if ((rc = ruart_rows_layernorm(pre, H, m->ln1_g[l], m->ln1_b[l], m->ln_eps, mid, H, dt, Rl, H, stream))) return rc;
-    if ((rc = gemm(mid, H, m->w_ff1[l], m->b_ff1[l], nullptr, ffn, dt, I, RUART_ACT_GELU, Rl))) return rc;
-    if ((rc = gemm(ffn, I, m->w_ff2[l], m->b_ff2[l], mid, pre, RUART_DT_F32, H, RUART_ACT_NONE, Rl))) return rc;
-    if ((rc = ruart_rows_layernorm(pre, H, m->ln2_g[l], m->ln2_b[l], m->ln_eps, out, H, dt, Rl, H, stream))) return rc;
+    if ((rc = gemm(a, H, m->w_ao[l], m->b_ao[l], res, w.pre, RUART_DT_F32, H, RUART_ACT_NONE, Rl))) return rc;
+    if ((rc = ruart_rows_layernorm(w.pre, H, m->ln1_g[l], m->ln1_b[l], m->ln_eps, w.mid, H, dt, Rl, H, stream))) return rc;
+    if ((rc = gemm(w.mid, H, m->w_ff1[l], m->b_ff1[l], nullptr, w.ffn, dt, I, RUART_ACT_GELU, Rl))) return rc;
+    if ((rc = gemm(w.ffn, I, m->w_ff2[l], m->b_ff2[l], w.mid, w.pre, RUART_DT_F32, H, RUART_ACT_NONE, Rl))) return rc;
+    if ((rc = ruart_rows_layernorm(w.pre, H, m->ln2_g[l], m->ln2_b[l], m->ln_eps, out, H, dt, Rl, H, stream))) return rc;
     in = out;
   }
-  ruart_prof_real_rows = 0;
   return 0;
 }

@@ -57,20 +57,8 @@ __global__ __launch_bounds__(256) void gemm_16_nt_128(const T16* __restrict__ A,
   const int wm = wave >> 1, wn = wave & 1;
   const int ntn = N / BN, ntm = M / BM;
   const int id = xcd_remap(blockIdx.x, gridDim.x);
-  // L2-friendly order inside an XCD's contiguous id range: groups of GROUP_M row panels, column-major inside a group,
-  // so a window of ~64 co-resident workgroups touches ~8 activation panels x ~8 weight panels instead of 64 + 64.
   int tm, tn;
-  if (order == 0) {
-    tm = id / ntn;
-    tn = id % ntn;
-  } else {
-    const int per_group = order * ntn;
-    const int g = id / per_group, first = g * order;
-    const int gsz = min(ntm - first, order);
-    const int r = id - g * per_group;
-    tm = first + r % gsz;
-    tn = r / gsz;
-  }
+  tile_of(id, ntm, ntn, order, tm, tn);          // L2-friendly order inside an XCD's contiguous id range (gemm_shared.h)
   const int m0 = tm * BM, n0 = tn * BN;
 
   // Direct-to-LDS staging (global_load_lds_dwordx4): one wave-instruction fills 1 KB = 8 tile rows of 128 B.  The LDS
@@ -166,17 +154,7 @@ __global__ __launch_bounds__(512, 2) void gemm_16_nt_256sq(const T16* __restrict
   const int ntn = N / BN4, ntm = M / BM4;
   const int id = xcd_remap(blockIdx.x, gridDim.x);
   int tm, tn;
-  if (order == 0) {
-    tm = id / ntn;
-    tn = id % ntn;
-  } else {
-    const int per_group = order * ntn;
-    const int g = id / per_group, first = g * order;
-    const int gsz = min(ntm - first, order);
-    const int r = id - g * per_group;
-    tm = first + r % gsz;
-    tn = r / gsz;
-  }
+  tile_of(id, ntm, ntn, order, tm, tn);
   const int m0 = tm * BM4, n0 = tn * BN4;
 
   const int srow = lane >> 3, schunk = (lane & 7) ^ srow;
@@ -412,21 +390,6 @@ __device__ __forceinline__ void p8_epilogue(f32x4_t (&acc)[4][8], char* smem, in
   }
 }
 
-// (tm, tn) of logical tile `id` under the GROUP_M walk (groups of `order` row panels, column-major inside a group)
-__device__ __forceinline__ void p8_tile_of(int id, int ntm, int ntn, int order, int& tm, int& tn) {
-  if (order == 0) {
-    tm = id / ntn;
-    tn = id % ntn;
-  } else {
-    const int per_group = order * ntn;
-    const int g = id / per_group, first = g * order;
-    const int gsz = min(ntm - first, order);
-    const int r = id - g * per_group;
-    tm = first + r % gsz;
-    tn = r / gsz;
-  }
-}
-
 // ------------------------------------------------------------------------------------------------
 // 256x256x64, four phases per K-tile with the prefetch in flight ACROSS barriers (the "8-phase" schedule of the CDNA4
 // playbook: 2 K-tiles = 8 phases per loop iteration).  Same tile, wave layout, swizzle and epilogue as gemm_16_nt_256sq.
@@ -470,22 +433,12 @@ __global__ __launch_bounds__(512, 2) void gemm_16_nt_256p8(const T16* __restrict
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // scalar: wave-dependent offsets stay in SGPRs
   const int wm = wave >> 2, wn = wave & 3;
   const int ntn = N / BN4, ntm = M / BM4;
-  // Workgroups [0, n_full) own whole tiles (XCD-contiguous walk); the rest of the grid are the K slices of the last tiles - the tail
-  // split of the launcher (p8_tail_plan, as in gemm_corr.hip): S workgroups per tile, dispatched last, each over nt / S K-tiles,
-  // parking its partial sums in `slabs` for gemm_16_fixup.  n_full == gridDim.x: no split (every other caller).
-  const int bid = blockIdx.x;
-  int id, slice = -1;
-  if (bid < n_full) {
-    id = xcd_remap(bid, n_full);
-  } else {
-    const int p = bid - n_full;
-    id = n_full + p / S;
-    slice = p - (p / S) * S;
-  }
-  id = __builtin_amdgcn_readfirstlane(id);           // (integer division runs on the vector ALU; dma16's operands must be scalar)
-  slice = __builtin_amdgcn_readfirstlane(slice);
+  // A whole tile, or - the tail split of the launcher (tail_plan, gemm_shared.h) - one of the S K slices of a last tile, each over
+  // nt / S K-tiles, parking its partial sums in `slabs` for gemm_16_fixup.  n_full == gridDim.x: no split (every other caller).
+  int id, slice;
+  tail_decode(blockIdx.x, n_full, S, id, slice);
   int tm, tn;
-  p8_tile_of(id, ntm, ntn, order, tm, tn);
+  tile_of(id, ntm, ntn, order, tm, tn);
   tm = __builtin_amdgcn_readfirstlane(tm);
   tn = __builtin_amdgcn_readfirstlane(tn);
   const int m0 = tm * BM4, n0 = tn * BN4;
@@ -621,12 +574,7 @@ __global__ __launch_bounds__(512, 2) void gemm_16_nt_256p8(const T16* __restrict
   RUART_BAR();                                                  // every wave is done reading operand tiles
 
   if (slice >= 0) {
-    // partial sums of this slice, thread-major ([i][j][tid] x 4 floats: 16-byte coalesced stores, read back the same way)
-    float* slab = slabs + ((size_t)(id - n_full) * S + slice) * (BM4 * BN4);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) *reinterpret_cast<f32x4_t*>(slab + ((i * 8 + j) * 512 + tid) * 4) = acc[i][j];
+    tail_store_slab(slabs, id - n_full, S, slice, acc);
     return;
   }
   p8_epilogue<T16, OUT_F32, RES, ACT, FK>(acc, smem, m0, n0, tm, bias, R, ldr, C, ldc, N, C2, colpart, 0, 4, fold);
@@ -870,7 +818,7 @@ __global__ __launch_bounds__(256, 1) void gemm_16_nt_256w4(const T16* __restrict
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
   int tm, tn;
-  p8_tile_of(__builtin_amdgcn_readfirstlane(xcd_remap(blockIdx.x, gridDim.x)), M / BM4, N / BN4, order, tm, tn);
+  tile_of(__builtin_amdgcn_readfirstlane(xcd_remap(blockIdx.x, gridDim.x)), M / BM4, N / BN4, order, tm, tn);
   tm = __builtin_amdgcn_readfirstlane(tm);
   tn = __builtin_amdgcn_readfirstlane(tn);
   const int m0 = tm * BM4, n0 = tn * BN4;
@@ -1007,83 +955,31 @@ __global__ __launch_bounds__(256, 1) void gemm_16_nt_256w4(const T16* __restrict
   }
 }
 
-// ---- tail split (see gemm_corr.hip: the same scheme for the plain 16-bit product) ---------------------------------------------------
+// ---- tail split (gemm_shared.h; gemm_corr.hip runs the same scheme for the fp16c product) -------------------------------------------
 // Second launch of a tail-split product: tile n_full + blockIdx.x = the sum of its S slices in slice order, then the tile's epilogue.
+static_assert(BM4 * BN4 == kTailTile, "the slabs of the tail split (gemm_shared.h) hold one tile of gemm_16_nt_256p8");
 template <typename T16, bool OUT_F32, int RES, int ACT>
-__global__ __launch_bounds__(512, 2) void gemm_16_fixup(const float* __restrict__ slabs, int S, int n_full, const float* __restrict__ bias,
+__global__ __launch_bounds__(kTailThreads, 2) void gemm_16_fixup(const float* __restrict__ slabs, int S, int n_full, const float* __restrict__ bias,
                                                         const void* __restrict__ R, int ldr, void* __restrict__ C, int ldc, int M, int N,
                                                         int order) {
-#define TILE_OF(id_, tm_, tn_) p8_tile_of(id_, M / BM4, N / BN4, order, tm_, tn_)
   extern __shared__ __attribute__((aligned(1024))) char smem[];
-  const int tid = threadIdx.x;
   const int q = blockIdx.x >> 2, hh = blockIdx.x & 3;       // one 32-rows-per-wave pass of the epilogue per workgroup
   int tm, tn;
-  TILE_OF(n_full + q, tm, tn);
-  const float* slab = slabs + (size_t)q * S * (BM4 * BN4);
+  tile_of(n_full + q, M / BM4, N / BN4, order, tm, tn);
   f32x4_t acc[4][8];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int hc = 0; hc < 4; ++hc) {
-    if (hc != hh) continue;                                  // (wave-uniform; keeps the accumulator indices static)
-    // slices in slice order, two slabs (16 loads per thread) in flight; the second of a pair is clamped and masked at an odd tail
-    for (int sl = 0; sl < S; sl += 2) {
-      const bool two = sl + 1 < S;
-      const float* p0 = slab + (size_t)sl * (BM4 * BN4);
-      const float* p1 = slab + (size_t)(two ? sl + 1 : sl) * (BM4 * BN4);
-      f32x4_t a[8], b[8];
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          a[i * 2 + j] = *reinterpret_cast<const f32x4_t*>(p0 + ((i * 8 + hc * 2 + j) * 512 + tid) * 4);
-          b[i * 2 + j] = *reinterpret_cast<const f32x4_t*>(p1 + ((i * 8 + hc * 2 + j) * 512 + tid) * 4);
-        }
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          acc[i][hc * 2 + j] += a[i * 2 + j];
-          if (two) acc[i][hc * 2 + j] += b[i * 2 + j];
-        }
-    }
-  }
+  tail_sum_slabs(slabs, q, S, hh, acc);
   p8_epilogue<T16, OUT_F32, RES, ACT>(acc, smem, tm * BM4, tn * BN4, tm, bias, R, ldr, C, ldc, N, nullptr, nullptr, hh, hh + 1);
-#undef TILE_OF
 }
 
-struct P8TailPlan { int n_full, r, S; };
-static P8TailPlan p8_tail_plan(int tiles, int nt, int cus) {
-  P8TailPlan p{tiles, 0, 0};
-  if (cus <= 0 || tiles <= cus) return p;
-  const int r = tiles % cus;
-  // the second launch (slab traffic, ~10 us) pays when the last round is nearly empty, or - up to 60 % full - when a tile is long (K >= 2048)
-  if (r == 0 || (4 * r > cus && !(5 * r <= 3 * cus && nt >= 32))) return p;
-  int S = cus / r;
-  if (S > 8) S = 8;
-  while (S >= 2 && (nt % S != 0 || (nt / S) % 2 != 0 || nt / S < 2)) --S;
-  if (S < 2) return p;
-  p.n_full = tiles - r;
-  p.r = r;
-  p.S = S;
-  return p;
-}
 extern "C" size_t ruart_gemm_16_tail_ws_bytes(int M, int N, int K, int cus) {
   if (M <= 0 || N <= 0 || K <= 0 || M % BM4 || N % BN4 || K % 128) return 0;
-  const P8TailPlan p = p8_tail_plan((M / BM4) * (N / BN4), K / BK, cus);
-  return (size_t)p.r * p.S * BM4 * BN4 * sizeof(float);
+  return tail_plan_bytes(tail_plan((M / BM4) * (N / BN4), K / BK, cus, false));
 }
-// workspace / planning CU count of the call in flight on THIS host thread (set by ruart_gemm_16_nt_ws around launch_gemm16; thread-local:
-// the autograd engine's thread and the main thread both enter the library)
-static thread_local void* g_tail_ws = nullptr;
-static thread_local size_t g_tail_ws_bytes = 0;
-static thread_local int g_tail_cus = 0;
 
+// tail_ws / tail_ws_bytes / cus: the slab workspace of ruart_gemm_16_nt_ws and the CU count its plan is made for (NULL: no tail split)
 template <typename T16, bool OF, int RS, int AC>
 static void launch_one(const T16* a, int lda, const T16* w, int ldw, const float* bias, const void* residual, int ldr, void* C, int ldc,
-                       int M, int N, int K, hipStream_t s) {
+                       int M, int N, int K, void* tail_ws, size_t tail_ws_bytes, int cus, hipStream_t s) {
   constexpr int lds = 2 * 2 * BM4 * BK * 2;              // 128 KB: both 256x256 kernels
   const bool sq = M % BM4 == 0 && N % BN4 == 0;
   if (g_gemm_variant == 7 && sq && K % BK == 0 && K >= 2 * BK && AC <= 1) {
@@ -1098,13 +994,7 @@ static void launch_one(const T16* a, int lda, const T16* w, int ldw, const float
     (void)done;
     // GROUP_M from the tile counts (ruart_tile_group_m, gemm_shared.h) until ruart_gemm_set_tile_order pins a value
     const int order = g_tile_order_auto ? ruart_tile_group_m(M / BM4, N / BN4, K, false) : g_tile_order;
-    const int tiles = (M / BM4) * (N / BN4);
-    P8TailPlan tp{tiles, 0, 0};
-    void* tail_ws = g_tail_ws;
-    if (tail_ws) {
-      tp = p8_tail_plan(tiles, K / BK, g_tail_cus);
-      if ((size_t)tp.r * tp.S * BM4 * BN4 * sizeof(float) > g_tail_ws_bytes) tp = P8TailPlan{tiles, 0, 0};
-    }
+    const TailPlan tp = tail_plan_ws((M / BM4) * (N / BN4), K / BK, cus, false, tail_ws, tail_ws_bytes);
     hipLaunchKernelGGL(kern, dim3(tp.n_full + tp.r * tp.S), dim3(512), lds, s, a, lda, w, ldw, bias, residual, ldr, C, ldc, M, N, K,
                        order, 0, (void*)nullptr, (float*)nullptr, tp.n_full, tp.S, (float*)tail_ws, CorrFold{});
     if (tp.r > 0) {
@@ -1128,10 +1018,11 @@ static void launch_one(const T16* a, int lda, const T16* w, int ldw, const float
 
 template <typename T16>
 static int launch_gemm16(const void* A, int lda, const void* W, int ldw, const float* bias, const void* residual, int ldr, int res,
-                         void* C, int ldc, bool of, int M, int N, int K, int act, hipStream_t s) {
+                         void* C, int ldc, bool of, int M, int N, int K, int act, void* tail_ws, size_t tail_ws_bytes, int cus,
+                         hipStream_t s) {
   const T16* a = (const T16*)A;
   const T16* w = (const T16*)W;
-#define LAUNCH(OF, RS, AC) launch_one<T16, OF, RS, AC>(a, lda, w, ldw, bias, residual, ldr, C, ldc, M, N, K, s)
+#define LAUNCH(OF, RS, AC) launch_one<T16, OF, RS, AC>(a, lda, w, ldw, bias, residual, ldr, C, ldc, M, N, K, tail_ws, tail_ws_bytes, cus, s)
   if (act == RUART_ACT_GELU) {
     if (res != 0) return (int)hipErrorInvalidValue;
     if (of) LAUNCH(true, 0, 1); else LAUNCH(false, 0, 1);
@@ -1150,17 +1041,6 @@ static int launch_gemm16(const void* A, int lda, const void* W, int ldw, const f
 extern "C" int ruart_gemm_16_nt_ws(const void* A, int lda, const void* W, int ldw, const float* bias, const void* residual, int ldr,
                                    int residual_dtype, void* C, int ldc, int out_dtype, int M, int N, int K, int act, int in_dtype,
                                    void* tail_ws, size_t tail_ws_bytes, int cus, void* stream) {
-  g_tail_ws = (tail_ws && cus > 0) ? tail_ws : nullptr;
-  g_tail_ws_bytes = tail_ws_bytes;
-  g_tail_cus = cus;
-  const int rc = ruart_gemm_16_nt(A, lda, W, ldw, bias, residual, ldr, residual_dtype, C, ldc, out_dtype, M, N, K, act, in_dtype, stream);
-  g_tail_ws = nullptr;
-  return rc;
-}
-
-extern "C" int ruart_gemm_16_nt(const void* A, int lda, const void* W, int ldw, const float* bias, const void* residual, int ldr,
-                                int residual_dtype, void* C, int ldc, int out_dtype, int M, int N, int K, int act, int in_dtype,
-                                void* stream) {
   RUART_ENTRY();
   if (M % BM || N % BN || K % BK || (lda & 7) || (ldw & 7) || (ldc & 3)) return (int)hipErrorInvalidValue;
   if (act != RUART_ACT_NONE && act != RUART_ACT_GELU) return (int)hipErrorInvalidValue;
@@ -1169,14 +1049,21 @@ extern "C" int ruart_gemm_16_nt(const void* A, int lda, const void* W, int ldw, 
   if (residual && residual_dtype != RUART_DT_F32 && residual_dtype != in_dtype) return (int)hipErrorInvalidValue;
   const int res = residual ? (residual_dtype == RUART_DT_F32 ? 2 : 1) : 0;
   const bool of = out_dtype == RUART_DT_F32;
+  if (cus <= 0) tail_ws = nullptr;
   void* rec = ruart_prof_begin_((hipStream_t)stream, M, N, K);
   int rc;
   if (in_dtype == RUART_DT_BF16)
-    rc = launch_gemm16<bf16_t>(A, lda, W, ldw, bias, residual, ldr, res, C, ldc, of, M, N, K, act, (hipStream_t)stream);
+    rc = launch_gemm16<bf16_t>(A, lda, W, ldw, bias, residual, ldr, res, C, ldc, of, M, N, K, act, tail_ws, tail_ws_bytes, cus, (hipStream_t)stream);
   else
-    rc = launch_gemm16<f16_t>(A, lda, W, ldw, bias, residual, ldr, res, C, ldc, of, M, N, K, act, (hipStream_t)stream);
+    rc = launch_gemm16<f16_t>(A, lda, W, ldw, bias, residual, ldr, res, C, ldc, of, M, N, K, act, tail_ws, tail_ws_bytes, cus, (hipStream_t)stream);
   ruart_prof_end_(rec, (hipStream_t)stream);
   return rc;
+}
+
+extern "C" int ruart_gemm_16_nt(const void* A, int lda, const void* W, int ldw, const float* bias, const void* residual, int ldr,
+                                int residual_dtype, void* C, int ldc, int out_dtype, int M, int N, int K, int act, int in_dtype,
+                                void* stream) {
+  return ruart_gemm_16_nt_ws(A, lda, W, ldw, bias, residual, ldr, residual_dtype, C, ldc, out_dtype, M, N, K, act, in_dtype, nullptr, 0, 0, stream);
 }
 
 // Training forward of the intermediate dense (Models/Bert/modeling.py:287-288): G = gelu(A . W^T + bias) AND the pre-activation H, both in

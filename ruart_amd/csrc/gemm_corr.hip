@@ -195,21 +195,6 @@ __device__ __forceinline__ void corr_epilogue(f32x4_t (&acc)[4][8], char* smem, 
   }
 }
 
-// (tm, tn) of logical tile `id` under the GROUP_M walk (groups of `order` row panels, column-major inside a group)
-__device__ __forceinline__ void corr_tile_of(int id, int ntm, int ntn, int order, int& tm, int& tn) {
-  if (order == 0) {
-    tm = id / ntn;
-    tn = id % ntn;
-  } else {
-    const int per_group = order * ntn;
-    const int g = id / per_group, first = g * order;
-    const int gsz = min(ntm - first, order);
-    const int r = id - g * per_group;
-    tm = first + r % gsz;
-    tn = r / gsz;
-  }
-}
-
 // (Capped at 224 architectural VGPRs - room for a co-resident small wave of another kernel - the compiler spills inside the K loop:
 // DESIGN.md section 5, round 4.)
 // EPI: 0 fp32 out; 1 fp32 out + fp32 residual; 2 GELU, split out (C = f16 rows, C8 = fp8 rows of 2N bytes)
@@ -228,23 +213,12 @@ __global__ __launch_bounds__(512, 2) void gemm_16c_nt_256p8(const char* __restri
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 2, wn = wave & 3;
   const int ntn = N / CBN, ntm = M / CBM;
-  // Workgroups [0, n_full) own whole tiles (XCD-contiguous walk over them); the rest of the grid are the K SLICES of the last
-  // tiles - the tail split of the launcher (corr_tail_plan): S workgroups per tile, dispatched last, each over NT / S K-tiles of
-  // one phase, parking its partial sums in `slabs` for gemm_16c_fixup.
-  const int bid = blockIdx.x;
-  int id, slice = -1;
-  if (bid < n_full) {
-    id = xcd_remap(bid, n_full);
-  } else {
-    const int p = bid - n_full;
-    id = n_full + p / S;
-    slice = p - (p / S) * S;
-  }
-  // (integer division runs on the vector ALU: pin the wave-uniform results to SGPRs, dma16's operands must be scalar)
-  id = __builtin_amdgcn_readfirstlane(id);
-  slice = __builtin_amdgcn_readfirstlane(slice);
+  // A whole tile, or - the tail split of the launcher (tail_plan, gemm_shared.h) - one of the S K SLICES of a last tile, each over
+  // NT / S K-tiles of one phase, parking its partial sums in `slabs` for gemm_16c_fixup.
+  int id, slice;
+  tail_decode(blockIdx.x, n_full, S, id, slice);
   int tm, tn;
-  corr_tile_of(id, ntm, ntn, order, tm, tn);
+  tile_of(id, ntm, ntn, order, tm, tn);
   tm = __builtin_amdgcn_readfirstlane(tm);
   tn = __builtin_amdgcn_readfirstlane(tn);
   const int m0 = tm * CBM, n0 = tn * CBN;
@@ -416,12 +390,7 @@ __global__ __launch_bounds__(512, 2) void gemm_16c_nt_256p8(const char* __restri
   RUART_BAR();                                                // every wave is done reading operand tiles
 
   if (slice >= 0) {
-    // partial sums of this slice, thread-major ([i][j][tid] x 4 floats: 16-byte coalesced stores, read back the same way)
-    float* slab = slabs + ((size_t)(id - n_full) * S + slice) * (CBM * CBN);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) *reinterpret_cast<f32x4_t*>(slab + ((i * 8 + j) * 512 + tid) * 4) = acc[i][j];
+    tail_store_slab(slabs, id - n_full, S, slice, acc);
     return;
   }
   corr_epilogue<EPI, FOLD>(acc, smem, m0, n0, bias, R, ldr, C, ldc, C8, N, 0, 4, f);
@@ -464,7 +433,7 @@ __global__ __launch_bounds__(256, 2) void gemm_16c_nt_256x128d(const char* __res
   const int ntn = N / DBN, ntm = M / CBM;
   int id = __builtin_amdgcn_readfirstlane(xcd_remap(blockIdx.x, gridDim.x));
   int tm, tn;
-  corr_tile_of(id, ntm, ntn, order, tm, tn);
+  tile_of(id, ntm, ntn, order, tm, tn);
   tm = __builtin_amdgcn_readfirstlane(tm);
   tn = __builtin_amdgcn_readfirstlane(tn);
   const int m0 = tm * CBM, n0 = tn * DBN;
@@ -614,49 +583,18 @@ __global__ __launch_bounds__(256, 2) void gemm_16c_nt_256x128d(const char* __res
 
 // Second launch of a tail-split product: tile n_full + blockIdx.x = the sum of its S slices IN SLICE ORDER (deterministic), then the
 // tile's epilogue exactly as the GEMM kernel runs it.
+static_assert(CBM * CBN == kTailTile, "the slabs of the tail split (gemm_shared.h) hold one tile of gemm_16c_nt_256p8");
 template <int EPI>
-__global__ __launch_bounds__(512, 2) void gemm_16c_fixup(const float* __restrict__ slabs, int S, int n_full, const float* __restrict__ bias,
+__global__ __launch_bounds__(kTailThreads, 2) void gemm_16c_fixup(const float* __restrict__ slabs, int S, int n_full, const float* __restrict__ bias,
                                                          const float* __restrict__ R, int ldr, void* __restrict__ C, int ldc,
                                                          unsigned char* __restrict__ C8, int M, int N, int order) {
-#define TILE_OF(id_, tm_, tn_) corr_tile_of(id_, M / CBM, N / CBN, order, tm_, tn_)
   extern __shared__ __attribute__((aligned(1024))) char smem[];
-  const int tid = threadIdx.x;
   const int q = blockIdx.x >> 2, hh = blockIdx.x & 3;       // one 32-rows-per-wave pass of the epilogue per workgroup
   int tm, tn;
-  TILE_OF(n_full + q, tm, tn);
-  const float* slab = slabs + (size_t)q * S * (CBM * CBN);
+  tile_of(n_full + q, M / CBM, N / CBN, order, tm, tn);
   f32x4_t acc[4][8];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int hc = 0; hc < 4; ++hc) {
-    if (hc != hh) continue;                                  // (wave-uniform; keeps the accumulator indices static)
-    // slices in slice order, two slabs (16 loads per thread) in flight; the second of a pair is clamped and masked at an odd tail
-    for (int sl = 0; sl < S; sl += 2) {
-      const bool two = sl + 1 < S;
-      const float* p0 = slab + (size_t)sl * (CBM * CBN);
-      const float* p1 = slab + (size_t)(two ? sl + 1 : sl) * (CBM * CBN);
-      f32x4_t a[8], b[8];
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          a[i * 2 + j] = *reinterpret_cast<const f32x4_t*>(p0 + ((i * 8 + hc * 2 + j) * 512 + tid) * 4);
-          b[i * 2 + j] = *reinterpret_cast<const f32x4_t*>(p1 + ((i * 8 + hc * 2 + j) * 512 + tid) * 4);
-        }
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          acc[i][hc * 2 + j] += a[i * 2 + j];
-          if (two) acc[i][hc * 2 + j] += b[i * 2 + j];
-        }
-    }
-  }
+  tail_sum_slabs(slabs, q, S, hh, acc);
   corr_epilogue<EPI>(acc, smem, tm * CBM, tn * CBN, bias, R, ldr, C, ldc, C8, N, hh, hh + 1, CorrFold{});
-#undef TILE_OF
 }
 
 // the epilogue's 32-bit byte offsets: the output (fp32 at most: 4 bytes per element; its split companions are smaller) and the residual
@@ -674,35 +612,10 @@ static inline int corr_tile_order(int M, int N, int K) {
 void* ruart_prof_begin_(hipStream_t s, int M, int N, int K);
 void ruart_prof_end_(void* rec, hipStream_t s);
 
-// ---- tail split ------------------------------------------------------------------------------------------------------------------
-// One 256 x 256 tile per CU means a product runs in whole ROUNDS of `cus` tiles, and the encoder's shapes do not fill their last one:
-// at the bench's 167 row tiles the N = 768 products are 501 tiles - on the 240 CUs of the run-ahead stream two full rounds and a
-// third of 21 tiles (2.09 -> 3 rounds: the mask cost the attention-output / output dense 44 % of their time), on all 256 CUs 1.96; the
-// (64, 512) north-star halves are 1.5 rounds.  With a workspace, the tiles of that last partial round are cut along K into S slices
-// each, dispatched behind the full tiles: r * S short workgroups instead of r full-length ones on an otherwise idle chip, then one
-// small launch (gemm_16c_fixup) adds a tile's slices in slice order and runs its epilogue.  Deterministic; the plan depends only on
-// (M, N, K, cus) - never on the stream the call happens to run on, so a pass on the CU-masked stream and an inline pass agree bit for bit.
-struct TailPlan { int n_full, r, S; };
-static TailPlan corr_tail_plan(int tiles, int NT, int cus) {
-  TailPlan p{tiles, 0, 0};
-  if (cus <= 0 || tiles <= cus) return p;                 // (a launch that is one partial round is left alone)
-  const int r = tiles % cus;
-  // the second launch (slab traffic, ~10 us) pays when the last round is nearly empty, or - up to 60 % full - when a tile is long (K >= 2048)
-  if (r == 0 || (4 * r > cus && !(5 * r <= 3 * cus && NT >= 64))) return p;
-  int S = cus / r;
-  if (S > 8) S = 8;                                        // slabs: S x 256 KB per tile, written and read once
-  S &= ~1;                                                 // even: a slice stays inside the f16 or the fp8 phase
-  while (S >= 2 && (NT % S != 0 || (NT / S) % 2 != 0 || NT / S < 2)) S -= 2;
-  if (S < 2) return p;
-  p.n_full = tiles - r;
-  p.r = r;
-  p.S = S;
-  return p;
-}
+// ---- tail split (gemm_shared.h): NT = 2 K / 64 K-tiles per tile, S even ------------------------------------------------------------
 extern "C" size_t ruart_gemm_16c_tail_ws_bytes(int M, int N, int K, int cus) {
   if (M <= 0 || N <= 0 || K <= 0 || M % CBM || N % CBN || K % 128) return 0;
-  const TailPlan p = corr_tail_plan((M / CBM) * (N / CBN), 2 * (K / 64), cus);
-  return (size_t)p.r * p.S * CBM * CBN * sizeof(float);
+  return tail_plan_bytes(tail_plan((M / CBM) * (N / CBN), 2 * (K / 64), cus, true));
 }
 
 template <int EPI, bool FOLD = false>
@@ -714,11 +627,7 @@ static void launch_corr(const void* A16, const void* A8, int lda, const void* W1
   const int nt = K / 64;
   const int n8 = corr == 3 ? nt : (corr ? nt / 2 : 0), o8 = corr == 2 ? nt / 2 : 0;
   const int tiles = (M / CBM) * (N / CBN), order = corr_tile_order(M, N, K);
-  TailPlan p{tiles, 0, 0};
-  if (corr == 3 && tail_ws) {
-    p = corr_tail_plan(tiles, 2 * nt, cus);
-    if ((size_t)p.r * p.S * CBM * CBN * sizeof(float) > tail_ws_bytes) p = TailPlan{tiles, 0, 0};
-  }
+  const TailPlan p = tail_plan_ws(tiles, 2 * nt, cus, true, corr == 3 ? tail_ws : nullptr, tail_ws_bytes);   // (the ablation forms never split)
   auto kern = gemm_16c_nt_256p8<EPI, FOLD>;
   static bool done = (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds), true);
   (void)done;

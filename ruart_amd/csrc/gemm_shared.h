@@ -1,4 +1,5 @@
-// Helpers shared by the encoder GEMM kernels (gemm.hip, gemm_corr.hip): LDS tile addressing, the GELU epilogue, raw barrier.
+// Helpers shared by the encoder GEMM kernels (gemm.hip, gemm_corr.hip, gemm_tn.hip): LDS tile addressing, the GELU epilogue, raw barrier,
+// the GROUP_M tile walk, the tail split (plan, slice decode, slab store, slab sum) and the LayerNorm fold.
 #pragma once
 #include "common.h"
 
@@ -69,6 +70,124 @@ static inline int ruart_tile_group_m(int row_tiles, int col_tiles, int K, bool p
   }
   if (row_tiles < 96 && !precise) g = 4;
   return g;
+}
+
+// (tm, tn) of logical tile `id` under the GROUP_M walk: groups of `order` row panels, column-major inside a group, so that a window of
+// ~64 co-resident workgroups touches ~8 activation panels x ~8 weight panels instead of 64 + 64 (order 0 = plain row-major)
+__device__ __forceinline__ void tile_of(int id, int ntm, int ntn, int order, int& tm, int& tn) {
+  if (order == 0) {
+    tm = id / ntn;
+    tn = id % ntn;
+  } else {
+    const int per_group = order * ntn;
+    const int g = id / per_group, first = g * order;
+    const int gsz = min(ntm - first, order);
+    const int r = id - g * per_group;
+    tm = first + r % gsz;
+    tn = r / gsz;
+  }
+}
+
+// ---- tail split of the 256 x 256 kernels (gemm_16_nt_256p8 / gemm_16_fixup, gemm_16c_nt_256p8 / gemm_16c_fixup) -----------------------
+// One 256 x 256 tile per CU means a product runs in whole ROUNDS of `cus` tiles, and the encoder's shapes do not fill their last one:
+// at the bench's 167 row tiles the N = 768 products are 501 tiles - on the 240 CUs of the run-ahead stream two full rounds and a
+// third of 21 tiles (2.09 -> 3 rounds: the mask cost the attention-output / output dense 44 % of their time), on all 256 CUs 1.96; the
+// (64, 512) north-star halves are 1.5 rounds.  With a workspace, the tiles of that last partial round are cut along K into S slices
+// each, dispatched behind the full tiles: r * S short workgroups instead of r full-length ones on an otherwise idle chip, then one
+// small launch (the fix-up kernel) adds a tile's slices in slice order and runs its epilogue.  Deterministic; the plan depends only on
+// (M, N, K, cus) - never on the stream the call happens to run on, so a pass on the CU-masked stream and an inline pass agree bit for bit.
+constexpr int kTailTile = 256 * 256;         // floats of one slab: the partial sums of one slice of one tile
+constexpr int kTailThreads = 512;            // threads of the kernels that write and sum slabs: acc[4][8] of four floats each
+static_assert(4 * 8 * 4 * kTailThreads == kTailTile, "a slab is the [4][8] accumulators of kTailThreads threads");
+struct TailPlan { int n_full, r, S; };       // tiles [0, n_full) whole, the last r in S slices each (r == 0: no split)
+static inline size_t tail_plan_bytes(const TailPlan& p) { return (size_t)p.r * p.S * kTailTile * sizeof(float); }
+// `kt`: K-tiles of a whole tile in the kernel's own unit - K / 64 in the plain kernel, 2 K / 64 (the f16 and the fp8 phase) in the fp16c
+// one, which also wants S even (a slice stays inside one phase).  A slice is an even number >= 2 of K-tiles.
+static inline TailPlan tail_plan(int tiles, int kt, int cus, bool even_S) {
+  TailPlan p{tiles, 0, 0};
+  if (cus <= 0 || tiles <= cus) return p;                 // (a launch that is one partial round is left alone)
+  const int r = tiles % cus;
+  const int long_kt = even_S ? 64 : 32;                   // K >= 2048 in either unit
+  // the second launch (slab traffic, ~10 us) pays when the last round is nearly empty, or - up to 60 % full - when a tile is long
+  if (r == 0 || (4 * r > cus && !(5 * r <= 3 * cus && kt >= long_kt))) return p;
+  const int step = even_S ? 2 : 1;
+  int S = cus / r;
+  if (S > 8) S = 8;                                        // slabs: S x 256 KB per tile, written and read once
+  S -= S % step;
+  while (S >= 2 && (kt % S != 0 || (kt / S) % 2 != 0 || kt / S < 2)) S -= step;
+  if (S < 2) return p;
+  p.n_full = tiles - r;
+  p.r = r;
+  p.S = S;
+  return p;
+}
+// the plan of a launch that was given `ws_bytes` of slab workspace at `ws`: no split without one, or with one too small for the plan
+static inline TailPlan tail_plan_ws(int tiles, int kt, int cus, bool even_S, const void* ws, size_t ws_bytes) {
+  TailPlan p{tiles, 0, 0};
+  if (!ws) return p;
+  p = tail_plan(tiles, kt, cus, even_S);
+  if (tail_plan_bytes(p) > ws_bytes) p = TailPlan{tiles, 0, 0};
+  return p;
+}
+
+// Workgroups [0, n_full) own whole tiles (XCD-contiguous walk over them); the rest of the grid are the K slices of the last tiles: S
+// workgroups per tile, dispatched last.  -> logical tile `id`, `slice` (-1: the whole tile), both wave-uniform in SGPRs (integer division
+// runs on the vector ALU; dma16's operands must be scalar).  n_full == gridDim.x: no split.
+__device__ __forceinline__ void tail_decode(int bid, int n_full, int S, int& id, int& slice) {
+  slice = -1;
+  if (bid < n_full) {
+    id = xcd_remap(bid, n_full);
+  } else {
+    const int p = bid - n_full;
+    id = n_full + p / S;
+    slice = p - (p / S) * S;
+  }
+  id = __builtin_amdgcn_readfirstlane(id);
+  slice = __builtin_amdgcn_readfirstlane(slice);
+}
+// partial sums of slice `slice` of split tile `q` (= id - n_full), thread-major ([i][j][tid] x 4 floats: 16-byte coalesced stores, read
+// back the same way by tail_sum_slabs)
+__device__ __forceinline__ void tail_store_slab(float* slabs, int q, int S, int slice, const f32x4_t (&acc)[4][8]) {
+  float* slab = slabs + ((size_t)q * S + slice) * kTailTile;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) *reinterpret_cast<f32x4_t*>(slab + ((i * 8 + j) * kTailThreads + threadIdx.x) * 4) = acc[i][j];
+}
+// acc = the sum of split tile q's S slices IN SLICE ORDER (deterministic), for the epilogue pass hh (accumulators [.][2 hh], [.][2 hh + 1])
+// only: a fix-up workgroup runs one 32-rows-per-wave pass.  The rest of acc is zero.
+__device__ __forceinline__ void tail_sum_slabs(const float* slabs, int q, int S, int hh, f32x4_t (&acc)[4][8]) {
+  const int tid = threadIdx.x;
+  const float* slab = slabs + (size_t)q * S * kTailTile;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int hc = 0; hc < 4; ++hc) {
+    if (hc != hh) continue;                                  // (wave-uniform; keeps the accumulator indices static)
+    // slices in slice order, two slabs (16 loads per thread) in flight; the second of a pair is clamped and masked at an odd tail
+    for (int sl = 0; sl < S; sl += 2) {
+      const bool two = sl + 1 < S;
+      const float* p0 = slab + (size_t)sl * kTailTile;
+      const float* p1 = slab + (size_t)(two ? sl + 1 : sl) * kTailTile;
+      f32x4_t a[8], b[8];
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          a[i * 2 + j] = *reinterpret_cast<const f32x4_t*>(p0 + ((i * 8 + hc * 2 + j) * kTailThreads + tid) * 4);
+          b[i * 2 + j] = *reinterpret_cast<const f32x4_t*>(p1 + ((i * 8 + hc * 2 + j) * kTailThreads + tid) * 4);
+        }
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          acc[i][hc * 2 + j] += a[i * 2 + j];
+          if (two) acc[i][hc * 2 + j] += b[i * 2 + j];
+        }
+    }
+  }
 }
 
 typedef const __attribute__((address_space(1))) void* gptr_t;

@@ -50,17 +50,7 @@ __global__ __launch_bounds__(512, 2) void gemm_16_tn_256p8(const T16* __restrict
   const int ntn = N / BN4, ntm = M / BM4;
   const int id = xcd_remap(blockIdx.x, gridDim.x);
   int tm, tn;
-  if (order == 0) {
-    tm = id / ntn;
-    tn = id % ntn;
-  } else {
-    const int per_group = order * ntn;
-    const int g = id / per_group, first = g * order;
-    const int gsz = min(ntm - first, order);
-    const int r = id - g * per_group;
-    tm = first + r % gsz;
-    tn = r / gsz;
-  }
+  tile_of(id, ntm, ntn, order, tm, tn);
   const int m0 = tm * BM4, n0 = tn * BN4;
 
   // staging: piece i (0, 1) of a wave is t-rows 8w + 4i .. +3; lane -> (row lane >> 4, LDS chunk lane & 15), fetching the source

@@ -406,6 +406,44 @@ def test_bert_long_sequences_and_split_groups(golden_dir, precision, tol):
                 assert err < tol, (precision, pack, gi, l, err)
 
 
+@pytest.mark.parametrize("precision,tol", [("fp16c", 5e-4), ("fp16", 1.5e-2)])
+def test_bert_unfolded_pass_with_tail_split(golden_dir, precision, tol):
+    """The unfolded passes with ruart_bert_model.tail_cus > 0: the slabs are carved behind the activations of the workspace and the QKV
+    product really splits (12 tiles planned for 11 CUs: one tile in the tail).  Model, groups and tolerances of
+    test_bert_long_sequences_and_split_groups - the split changes only the fp32 summation order inside a product."""
+    from ruart_amd.bert import BertEncoderWeights, PackedTokens, bert_encode, _Buffers
+    lib = hip.load()
+    hid, cus = 256, 11
+    cfg = synth.bert_config(vocab_size=300, hidden_size=hid, num_hidden_layers=2, num_attention_heads=hid // 64, intermediate_size=2 * hid,
+                            max_position_embeddings=256)
+    w = synth.make_bert_weights(cfg, seed=3, w_std=0.08)
+    g = np.random.default_rng(0)
+    lens_a, lens_b = [200, 65, 64, 1, 130], [7, 3, 256, 129]
+    def mk(lens, L):
+        ids = np.zeros((len(lens), L), dtype=np.int64)
+        for i, l in enumerate(lens):
+            ids[i, :l] = g.integers(1, 300, size=l)
+        return T(ids), T(ids != 0)
+    ga, gb = mk(lens_a, 200), mk(lens_b, 256)
+    d = dev()
+    W = BertEncoderWeights(w, cfg, d, precision, ln_fold=False)
+    W.c_model.tail_cus = cus
+    packed = PackedTokens([ga, gb], d, pack=True, mfma_long=precision == "fp16")
+    assert packed.Tp == 1024
+    tail_ws_bytes = lib.ruart_gemm_16c_tail_ws_bytes if precision == "fp16c" else lib.ruart_gemm_16_tail_ws_bytes
+    assert tail_ws_bytes(packed.Tp, 3 * hid, hid, cus) > 0
+    layers = bert_encode(W, packed, _Buffers()).float().cpu()
+    wt = {k: T(v) for k, v in w.items()}
+    for gi, (ids, mask) in enumerate((ga, gb)):
+        with torch.no_grad():
+            ref = O.bert_forward(wt, cfg, ids, mask)
+        idx = T(packed.group_index[gi])
+        for l in range(2):
+            err = maxerr(layers[l][idx[mask]], ref[l][mask])
+            print("tail split %s group %d layer %d: max abs err %.3e" % (precision, gi, l, err))
+            assert err < tol, (precision, gi, l, err)
+
+
 def test_bert_rows_longer_than_512_are_windowed(golden_dir):
     """``Bert.forward`` on rows of up to 600 word pieces against the oracle's restatement of the reference's 512-windowing
     (Models/Bert/Bert.py:133-138: independent windows, positions restart), incl. a word whose pieces straddle the boundary and
