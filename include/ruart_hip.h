@@ -243,6 +243,13 @@ int ruart_mix_rows(const void* layers16, long long layer_stride, int ld, int n_l
                    void* stream);
 int ruart_mix_rows_bwd(const void* layers16, long long layer_stride, int ld, int n_layers, const float* g, int ldg, float* d_w, float* ws,
                        int rows, int H, void* stream);
+/* opt['bert_train_layers']: the hand-over from the frozen lower layers (ruart_bert_forward_folded: y [n_layers][rows][H] fp32 PRE-LayerNorm
+ * rows, ln_stats [n_layers][stats_stride][2] = (mu, rstd), ln_gamma / ln_beta [n_layers][H]) to the trained upper ones:
+ * out16[l][row] = f16((y - mu) rstd gamma_l + beta_l) for row < n_tokens, zeros for n_tokens <= row < rows - the first n_layers planes of
+ * the f16 block the first trained layer and ruart_mix_rows / _bwd read.  H % 4 == 0, H <= 1024; y 16-byte, out16 8-byte aligned. */
+int ruart_rows_ln_to_16(const float* y, long long layer_stride, int ldy, const float* ln_stats, long long stats_stride, const float* ln_gamma,
+                        const float* ln_beta, void* out16, long long out_stride, int ldo, int n_layers, int n_tokens, int rows, int H,
+                        void* stream);
 /* Models/Bert/modeling.py:224-250 for training: windows of whole sequences (<= 64 word pieces per block [blk_q0, blk_q1), keys = the same
  * tokens), f16 [Q | K | V] rows in (Q pre-scaled), f16 context rows out, attention-probability dropout p_drop from `seed`; the backward
  * takes the context gradient (bf16) and writes [dQ | dK | dV] rows (bf16), recomputing the probabilities; bias_part (optional,

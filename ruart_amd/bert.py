@@ -196,6 +196,44 @@ class BertEncoderWeights:
         return self.cfg["num_hidden_layers"]
 
 
+def train_layer_split(opt, n_layers):
+    """``opt['bert_train_layers'] = N`` in a conf without LOCK_BERT: only the top N encoder layers train.  Returns k = n_layers - N, the
+    number of frozen lower layers (layers 0 .. k-1 and the embeddings with their LayerNorm); 0 without the key or with N = n_layers - the
+    fully trainable encoder, unchanged.  Pure (no device): every combination the partial encoder does not serve is refused here."""
+    if "bert_train_layers" not in opt:
+        return 0
+    n = opt["bert_train_layers"]
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1 or n > n_layers:
+        raise ValueError("opt['bert_train_layers'] = %r: the number of trained top layers is an integer in 1 .. %d" % (n, n_layers))
+    if "LOCK_BERT" in opt:
+        raise ValueError("opt['bert_train_layers'] trains encoder layers, LOCK_BERT freezes all of them: a conf has one or the other")
+    if str(opt.get("bert_train_gemm", "x3")) != "16":
+        raise ValueError("opt['bert_train_layers'] cuts the 16-bit trainable encoder only: it needs opt['bert_train_gemm'] = '16' (got %r)"
+                         % (opt.get("bert_train_gemm", "x3"),))
+    if opt.get("bert_no_pack", False):
+        raise ValueError("opt['bert_train_layers'] runs on the packed token stream: it does not combine with opt['bert_no_pack']")
+    return int(n_layers) - int(n)
+
+
+class LowerLayers:
+    """The first ``k`` layers of a ``BertEncoderWeights`` as an encoder of their own (``bert_encode`` takes it): the same device tensors,
+    a copy of the C struct with ``n_layers = k``.  The operand set of the frozen lower part under ``opt['bert_train_layers']``."""
+
+    def __init__(self, weights, k):
+        if not 0 < k <= weights.n_layers:
+            raise ValueError("the lower part holds 1 .. %d layers, not %d" % (weights.n_layers, k))
+        self.full = weights                  # owns the tensors and the pointer arrays the struct refers to
+        self.cfg, self.device, self.precision = weights.cfg, weights.device, weights.precision
+        self.dtype, self.tdtype, self.corr8, self.ln_fold = weights.dtype, weights.tdtype, weights.corr8, weights.ln_fold
+        self.hidden, self.n_layers = weights.hidden, int(k)
+        m = hip.BertModelC()
+        ctypes.memmove(ctypes.byref(m), ctypes.byref(weights.c_model), ctypes.sizeof(m))
+        m.n_layers = int(k)
+        self.c_model = m
+        if self.ln_fold:
+            self.ln2_g_all, self.ln2_b_all = weights.ln2_g_all[:k], weights.ln2_b_all[:k]
+
+
 class PackedTokens:
     """One step's word pieces as a packed stream + the descriptors the kernels need.
 
@@ -596,6 +634,7 @@ class Bert(nn.Module):
             fold = False                     # the sub-word pooling kernels read pre-LayerNorm rows in fp32 only: the plain 16-bit folded pass
                                              # (round 6) serves whole-sequence encoding (bert_encode, bench.py --mode bert512), not this class
         self.weights = BertEncoderWeights(state, cfg, self._device, precision, ln_fold=fold)
+        self.n_frozen = train_layer_split(opt, cfg["num_hidden_layers"])      # opt['bert_train_layers']: frozen lower layers (0: none)
         self.bert_model = None               # trainable fp32 encoder (bert_train.BertModelTrainable) once ``unlock`` is called
         self._source = (state, cfg)          # kept until SDNet has decided between the frozen and the trainable path
         self.pack = not opt.get("bert_no_pack", False)
@@ -630,9 +669,20 @@ class Bert(nn.Module):
             self.bert_model = BertModelTrainable16(state, cfg, self._device)
             # passes without active dropout (evaluation, parity tests) on the frozen path's fp16c kernels: 1e-3 with the encoder unlocked
             self.bert_model.accurate_forward = bool(self.opt.get("bert_train_accurate_fwd", True))
+            if self.n_frozen and self.weights.precision != "fp16c":
+                raise ValueError("opt['bert_train_layers']: the frozen lower layers run on the fp16c kernels (bert_precision = %r)"
+                                 % (self.weights.precision,))
+            if self.n_frozen:
+                # opt['bert_train_layers']: layers below the cut and the embeddings stay what the checkpoint holds - their passes with
+                # active dropout run deterministically on the frozen path's kernels (what ``lock`` says about the eval call applies
+                # to them too), on this module's operand set, and may run one step ahead (``prefetch``)
+                self._lower_weights = LowerLayers(self.weights, self.n_frozen)
+                self.bert_model.freeze_below(self.n_frozen, self.lower_layers_for)
         else:
             # "x3": fp32-class graph (pins parity); "16gemm": the same graph with the two row-parallel products of every projection on
             # the frozen path's 16-bit MFMA GEMM
+            if self.n_frozen:
+                raise ValueError("opt['bert_train_layers'] needs hidden / intermediate sizes that are multiples of 256")
             self.bert_model = BertModelTrainable(state, cfg, self._device, gemm="16" if mode in ("16", "16gemm") else "x3")
         self._source = None
 
@@ -714,9 +764,13 @@ class Bert(nn.Module):
     def prefetch(self, packed, after_stream=None):
         """Encode ``packed`` asynchronously into the buffer set the current step does NOT use; ``layers_for`` returns the
         result.  ``after_stream``: the stream whose already enqueued work (the previous consumers of that set) must finish
-        first.  Call it after ``layers_for`` of the current batch."""
-        if getattr(packed, "_layers", None) is not None or getattr(self, "bert_model", None) is not None or self._frozen_dropout_active():
+        first.  Call it after ``layers_for`` of the current batch.  With ``opt['bert_train_layers']`` the pass is the one of the frozen
+        lower layers (``runs_ahead``), picked up by ``lower_layers_for`` from inside the trainable encoder's forward."""
+        lower = self.runs_ahead()            # opt['bert_train_layers']: the frozen lower layers of a partly trained encoder
+        if getattr(packed, "_layers", None) is not None or (getattr(self, "bert_model", None) is not None and not lower) \
+                or self._frozen_dropout_active():
             return                           # (a trainable encoder changes every step, a dropout pass is drawn per step: nothing to run ahead)
+        weights = self._lower_weights if lower else self.weights
         dev = self._device
         cus = self.prefetch_cus(packed)
         st = self._pf_streams.get(cus)
@@ -741,7 +795,7 @@ class Bert(nn.Module):
         self._pending = packed
         with torch.cuda.stream(st):
             packed._set = self._in_use ^ 1
-            packed._layers = bert_encode(self.weights, packed, self._bufsets[packed._set])
+            packed._layers = bert_encode(weights, packed, self._bufsets[packed._set])
             packed._event = self._last_pf_event = st.record_event()
 
     def close(self, destroy=None):
@@ -775,6 +829,21 @@ class Bert(nn.Module):
                 model = self.__dict__["_dropout_model"]
                 fast = model.layers_nograd(packed, training=True) if hasattr(model, "layers_nograd") else None
                 return fast if fast is not None else model(packed, training=True)
+        return self._pickup(packed, self.weights)
+
+    def runs_ahead(self):
+        """True while the frozen lower layers of a partly trained encoder (``opt['bert_train_layers']``) run one step ahead: in training,
+        when the step's pass is the mixed-kernel one (``BertModelTrainable16.mixed_pass``), unless ``opt['bert_train_prefetch']`` is False."""
+        model = getattr(self, "bert_model", None)
+        return bool(model is not None and self.n_frozen and self.training and self.opt.get("bert_train_prefetch", True)
+                    and model.mixed_pass(True))
+
+    def lower_layers_for(self, packed):
+        """Output of the frozen lower layers for ``packed`` (what ``bert_encode`` returns for ``LowerLayers``): the pass that ran ahead, or
+        computed now.  The tensor lives in one of the two buffer sets: consume it before the next step's call."""
+        return self._pickup(packed, self._lower_weights)
+
+    def _pickup(self, packed, weights):
         layers = getattr(packed, "_layers", None)
         if layers is not None:
             torch.cuda.current_stream(self._device).wait_event(packed._event)
@@ -787,7 +856,7 @@ class Bert(nn.Module):
         if pend is None or getattr(pend, "_layers", None) is None or pend._set != self._in_use ^ 1:
             self._in_use ^= 1                # else: the other set holds a pass still to be consumed - reuse the current one
         self._pickup_event = torch.cuda.current_stream(self._device).record_event()
-        return bert_encode(self.weights, packed, self._bufsets[self._in_use])
+        return bert_encode(weights, packed, self._bufsets[self._in_use])
 
     # -- fused path used by ruart_amd.SDNet -------------------------------------------------------------
     def encode(self, groups):

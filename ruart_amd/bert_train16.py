@@ -26,6 +26,11 @@ Accuracy class: mixed-precision training - f16 activations, bf16 gradients, fp32
 gradient (tests hold every parameter-gradient norm of the reference's backward to 3 %).  Sequences longer than 64 word pieces (up to the
 512 of Models/Bert/Bert.py:96-99) are cut into 64-token chunks that attend to their whole sequence (``ruart_attn_train_fwd_long`` /
 ``_bwd_long``); only a stream with a key bias (the unpacked -10000 mode) still takes the fp32-class path of bert_train.py.
+
+``opt['bert_train_layers'] = N`` (``freeze_below``): the embeddings and the layers below k = n_layers - N are frozen.  A pass with
+active dropout takes their outputs from the frozen path's fp16c pass (``bert.Bert.lower_layers_for``: deterministic, possibly run one
+step ahead), ``ruart_rows_ln_to_16`` hands them over as the first k planes of the f16 layer block, and the layers from k on run as
+above; nothing is saved below k.  Every backward pass ends with layer k: no dX product into layer k-1, no embedding backward.
 """
 import numpy as np
 import torch
@@ -58,6 +63,7 @@ class _Run:
         self.dev = packed.ids.device
         self.T, self.Tp = packed.T, packed.Tp
         self.H, self.NL, self.nh = model.hidden, model.n_layers, model.n_heads
+        self.k = model.n_frozen                                       # layers below k and the embeddings are frozen (0: none)
         self.I = int(model.cfg["intermediate_size"])
         self.p_h = model.p_hidden if training else 0.0
         self.p_a = model.p_attn if training else 0.0
@@ -173,6 +179,22 @@ class _Run:
             + P["embeddings.token_type_embeddings.weight"][0]
         return self._ln_fwd(e, None, P["embeddings.LayerNorm.gamma"], P["embeddings.LayerNorm.beta"], self.p_h, self._seed(-1, 0), post=1)
 
+    def _lower_fwd(self):
+        """The frozen layers 0 .. k-1 on the frozen path's kernels (``bert.Bert.lower_layers_for``: picked up from the pass that ran one
+        step ahead, or computed now), handed over as the first k planes of ``self.layers``; returns plane k-1, the input of layer k."""
+        lib, T, Tp, H, k = self.lib, self.T, self.Tp, self.H, self.k
+        low = self.m._lower(self.packed)
+        ln = getattr(low, "_ln", None)
+        if ln is not None:                  # folded pass: pre-LayerNorm fp32 rows + (mu, rstd) + the output LayerNorms' tables
+            stats, g, b = ln
+            _chk(lib.ruart_rows_ln_to_16(hip.ptr(low), Tp * H, H, hip.ptr(stats), Tp, hip.ptr(g), hip.ptr(b), hip.ptr(self.layers), Tp * H, H, k,
+                                         T, Tp, H, self._st()), "ruart_rows_ln_to_16")
+        elif low.dtype == torch.float32:    # unfolded fp16c pass (opt['bert_ln_fold'] = 0, a tail split): finished fp32 rows, pad rows zero
+            _chk(lib.ruart_cast_f32_to_16(hip.ptr(low), hip.ptr(self.layers), hip.DT_F16, k * Tp * H, 1.0, self._st()), "ruart_cast_f32_to_16")
+        else:
+            raise ValueError("opt['bert_train_layers']: the frozen lower layers run in the fp16c precision")
+        return self.layers[k - 1]
+
     # -- the accurate forward: fp16c kernels of the frozen path on the live parameters -------------------------------------------
     def _forward_accurate(self, layer_w):
         """A pass WITHOUT active dropout (evaluation, and the parity tests: Models/Bert/modeling.py's dropouts are identities there) is
@@ -204,12 +226,15 @@ class _Run:
         self.recompute = False
         if self.p_h == 0.0 and self.p_a == 0.0 and self.m.accurate_forward:
             return self._forward_accurate(layer_w)
-        x16, self.pre_e, self.st_e = self._embed_fwd()
-        self.x_in = x16                                               # input of layer 0
         self.layers = torch.empty(NL, Tp, H, dtype=torch.float16, device=self.dev)
+        if self.k:
+            x16 = self._lower_fwd()                                   # frozen layers 0 .. k-1 -> the first k planes; input of layer k
+        else:
+            x16, self.pre_e, self.st_e = self._embed_fwd()
+            self.x_in = x16                                           # input of layer 0
         self.saved = {}
         self.wT = {}
-        for l in range(NL):
+        for l in range(self.k, NL):
             saved = self._layer_fwd(l, x16, self.layers[l])
             if self.keep:
                 self.saved[l] = saved
@@ -294,10 +319,12 @@ class _Run:
         dqkv = torch.zeros(Tp, 3 * H, dtype=torch.bfloat16, device=dev)                 # pad rows stay zero
         dX = torch.zeros(Tp, H, dtype=torch.float32, device=dev)
         blk_q0, blk_q1 = plan["win"]
+        k = self.k                                                                       # the backward ends with layer k (0: the embeddings)
         if self.recompute:                                                               # (accurate forward: only layer outputs were kept)
-            self.x_in, self.pre_e, self.st_e = self._embed_fwd()
+            if not k:
+                self.x_in, self.pre_e, self.st_e = self._embed_fwd()
             scratch = self._new(Tp, H, torch.float16)
-        for l in range(NL - 1, -1, -1):
+        for l in range(NL - 1, k - 1, -1):
             pre = "encoder.layer.%d." % l
             a = pre + "attention.self."
             x16 = self.layers[l - 1] if l > 0 else self.x_in
@@ -352,9 +379,13 @@ class _Run:
             grads[a + "query.bias"], grads[a + "key.bias"], grads[a + "value.bias"] = db[:H] * scale, torch.zeros_like(db[:H]), db[H:]
             grads[a + "query.weight"], grads[a + "key.weight"], grads[a + "value.weight"] = self._dw(
                 dqkv, self._bf16(x16), row_scales=[(H, scale), (H, 1.0), (H, 1.0)])
-            dX = self._gemm(dqkv, w_qkv_t, None, self._new(Tp, H, torch.float32), hip.DT_BF16, res=d_res1)
+            if l > k or not k:                                                            # (nothing below a frozen layer k-1 wants its gradient)
+                dX = self._gemm(dqkv, w_qkv_t, None, self._new(Tp, H, torch.float32), hip.DT_BF16, res=d_res1)
             self.saved.pop(l, None)                                                       # release this layer's activations
             self.wT.pop(l, None)
+        self.xb = self.part = None
+        if k:
+            return d_lw, grads
         # ---- embeddings: dropout(LayerNorm(word + position + type))
         d_e, _, dge, dbe, _ = self._ln_bwd(dX, None, None, self.pre_e, self.st_e, P["embeddings.LayerNorm.gamma"], self.p_h, self._seed(-1, 0), post=1)
         grads["embeddings.LayerNorm.gamma"], grads["embeddings.LayerNorm.beta"] = dge, dbe
@@ -365,7 +396,6 @@ class _Run:
         gt = torch.zeros_like(P["embeddings.token_type_embeddings.weight"])
         gt[0] = d_e.sum(0)
         grads["embeddings.token_type_embeddings.weight"] = gt
-        self.xb = self.part = None
         return d_lw, grads
 
 
@@ -399,6 +429,25 @@ class BertModelTrainable16(BertModelTrainable):
         missing = [n for n in self._order if n not in self._p]
         if missing:
             raise ValueError("checkpoint lacks encoder tensors: %s" % missing[:3])
+
+    n_frozen = 0                     # opt['bert_train_layers']: the embeddings and layers 0 .. n_frozen-1 are frozen (freeze_below)
+
+    def freeze_below(self, k, lower):
+        """Freeze the embeddings (with their LayerNorm) and the layers 0 .. k-1: their parameters keep their names and lose
+        ``requires_grad``.  ``lower(packed)``: their outputs for a packed stream, as ``bert.bert_encode`` returns them for those k layers
+        (``bert.Bert.lower_layers_for``)."""
+        if not 0 < k < self.n_layers:
+            raise ValueError("freeze_below: 1 .. %d layers can be frozen, not %d" % (self.n_layers - 1, k))
+        self.n_frozen = int(k)
+        self.__dict__["_lower"] = lower
+        for n in self._order[:len(_EMB_TENSORS) + k * len(_LAYER_TENSORS)]:
+            self._p[n].requires_grad_(False)
+
+    def mixed_pass(self, training):
+        """True when a pass of this mode runs the f16 training kernels (active dropout, or ``accurate_forward`` off) - with frozen
+        lower layers the pass that takes them from the frozen path's kernels; False: the whole fp16c pass over the live parameters."""
+        drop = training and (self.p_hidden > 0.0 or self.p_attn > 0.0)
+        return bool(drop or not self.accurate_forward)
 
     accurate_forward = True          # passes without active dropout run the frozen path's fp16c kernels (bert.Bert.unlock sets it from opt)
 

@@ -15,6 +15,8 @@
 //                                  hold the two forms against each other)
 //   ruart_splitk_reduce            sums the fp32 partial slabs of a split-K GEMM (fixed order: deterministic)
 //   ruart_mix_rows / _bwd          mixed[r] = sum_l w[l] * layer_l[r] (Models/SDNet.py:573-581 on the token stream) and d w[l]
+//   ruart_rows_ln_to_16            the frozen lower layers' PRE-LayerNorm fp32 rows (ruart_bert_forward_folded) -> the normalised f16 layer
+//                                  outputs the first trained layer and the layer mix read (opt['bert_train_layers'])
 #include "common.h"
 #include "ruart_hip.h"
 
@@ -606,6 +608,72 @@ extern "C" int ruart_mix_rows_bwd(const void* layers16, long long layer_stride, 
   hipLaunchKernelGGL(mix_rows_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const f16_t*)layers16, (size_t)layer_stride, ld, n_layers,
                      g, ldg, ws, rows, H);
   colreduce(ws, blocks, (size_t)n_layers, d_w, n_layers, 0, (hipStream_t)stream);
+  RUART_CHECK_LAUNCH();
+  return 0;
+}
+
+// Hand-over from the frozen lower layers (the folded fp16c pass: PRE-LayerNorm fp32 rows y, (mu, rstd) per row, the output LayerNorms'
+// gamma / beta tables) to the trained upper ones: out[l][row] = f16((y - mu) rstd gamma_l + beta_l) for n_layers layers in one launch,
+// rows n_tokens .. rows - 1 as zeros.  One wave per row, blockIdx.y = layer; 4 bytes read and 2 written per element.  The row's statistics
+// are one 8-byte load per lane (the same address across the wave: a VGPR pair, no scalar path).  The rounding errors of y - mu and of
+// its product with rstd are carried along (two-sum and fma residuals, ~10 more fp32 operations per element of an HBM-bound pass), so
+// a result that gamma x and beta nearly cancel to is still good to an fp32 ulp of ITSELF: what is stored is the f16 rounding of the
+// exact value or its neighbour, whatever its size.
+__global__ __launch_bounds__(256) void rows_ln_to_16_kernel(const float* __restrict__ y, size_t layer_stride, int ldy,
+                                                            const float2* __restrict__ stats, size_t stats_stride,
+                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                            f16_t* __restrict__ out, size_t out_stride, int ldo, int n_tokens, int rows, int H) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int l = blockIdx.y;
+  if (row >= rows) return;
+  f16_t* o = out + (size_t)l * out_stride + (size_t)row * ldo;
+  if (row >= n_tokens) {
+#pragma unroll
+    for (int i = 0; i < TMAXG; ++i) {
+      const int c = (i * 64 + lane) * 4;
+      if (c < H) store4(o + c, (f32x4_t){0.f, 0.f, 0.f, 0.f});
+    }
+    return;
+  }
+  const float2 st = stats[(size_t)l * stats_stride + row];
+  const float* src = y + (size_t)l * layer_stride + (size_t)row * ldy;
+  f32x4_t v[TMAXG];
+#pragma unroll
+  for (int i = 0; i < TMAXG; ++i) {
+    const int c = (i * 64 + lane) * 4;
+    if (c < H) v[i] = load4_stream(src + c);
+  }
+#pragma unroll
+  for (int i = 0; i < TMAXG; ++i) {
+    const int c = (i * 64 + lane) * 4;
+    if (c < H) {
+      const f32x4_t g = load4(gamma + (size_t)l * H + c), b = load4(beta + (size_t)l * H + c);
+      f32x4_t r;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const float yv = v[i][k], d = yv - st.x, bb = d - yv;
+        const float ed = (yv - (d - bb)) - (st.x + bb);                                  // y - mu = d + ed exactly
+        const float t = d * st.y;
+        const float et = __builtin_fmaf(ed, st.y, __builtin_fmaf(d, st.y, -t));        // (y - mu) rstd = t + et to second order
+        r[k] = __builtin_fmaf(g[k], et, __builtin_fmaf(g[k], t, b[k]));
+      }
+      store4(o + c, r);
+    }
+  }
+}
+
+extern "C" int ruart_rows_ln_to_16(const float* y, long long layer_stride, int ldy, const float* ln_stats, long long stats_stride,
+                                   const float* ln_gamma, const float* ln_beta, void* out16, long long out_stride, int ldo, int n_layers,
+                                   int n_tokens, int rows, int H, void* stream) {
+  RUART_ENTRY();
+  if (!y || !ln_stats || !ln_gamma || !ln_beta || !out16 || H % 4 || H <= 0 || H > 256 * TMAXG || rows <= 0 || n_tokens < 0 || n_tokens > rows ||
+      n_layers <= 0 || n_layers > 65535 || ldy < H || ldo < H || ldy % 4 || ldo % 4 || layer_stride % 4 || out_stride % 4 ||
+      layer_stride < (long long)rows * ldy - (ldy - H) || out_stride < (long long)rows * ldo - (ldo - H) || stats_stride < rows ||
+      ((uintptr_t)y & 15) || ((uintptr_t)out16 & 7) || ((uintptr_t)ln_gamma & 15) || ((uintptr_t)ln_beta & 15) || ((uintptr_t)ln_stats & 7))
+    return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(rows_ln_to_16_kernel, dim3(ceil_div(rows, 4), n_layers), dim3(256), 0, (hipStream_t)stream, y, (size_t)layer_stride, ldy,
+                     (const float2*)ln_stats, (size_t)stats_stride, ln_gamma, ln_beta, (f16_t*)out16, (size_t)out_stride, ldo, n_tokens, rows, H);
   RUART_CHECK_LAUNCH();
   return 0;
 }

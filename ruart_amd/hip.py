@@ -92,6 +92,7 @@ _SIGNATURES = {
     "ruart_splitk_reduce": (_I, [_P, _LL, _I, _P, _LL, _F, _I, _P]),
     "ruart_mix_rows": (_I, [_P, _LL, _I, _I, _P, _P, _I, _I, _I, _P]),
     "ruart_mix_rows_bwd": (_I, [_P, _LL, _I, _I, _P, _I, _P, _P, _I, _I, _P]),
+    "ruart_rows_ln_to_16": (_I, [_P, _LL, _I, _P, _LL, _P, _P, _P, _LL, _I, _I, _I, _I, _I, _P]),
     "ruart_attn_train_fwd": (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _F, ctypes.c_uint, _P]),
     "ruart_attn_train_bwd": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _F, ctypes.c_uint, _P, _P]),
     "ruart_attn_train_fwd_long": (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _F, ctypes.c_uint, _P, _P]),

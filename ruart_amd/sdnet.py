@@ -283,7 +283,8 @@ class SDNet(nn.Module):
 
     def prefetch_bert(self, q_list, ocr_list, od_list):
         """Ask the next ``forward`` to start the (frozen) BERT pass of this FUTURE batch on the encoder's own stream, right
-        after it has picked up its own encoder output (see Bert.prefetch)."""
+        after it has picked up its own encoder output (see Bert.prefetch).  A partly trained encoder (opt['bert_train_layers']) runs
+        its frozen lower layers ahead the same way; a fully trained one has nothing to run ahead."""
         self._next_batch = (q_list, ocr_list, od_list)
 
     def launch_prefetch(self):

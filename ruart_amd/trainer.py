@@ -177,6 +177,17 @@ class BaseTrainer:
             fw.writelines(f)
 
 
+def predict_checkpoint_keys(keys, opt, trained=()):
+    """The keys ``save_for_predict`` writes, in order: the reference's set (Models/SDNetTrainer.py:492-509 drops every contextual
+    encoder's and the fixed embeddings' tensors) and - with ``opt['bert_train_layers']``, and only then - the ``Bert.bert_model.*``
+    tensors among ``trained`` (the names of the parameters with ``requires_grad``): the encoder layers this conf trains, which the
+    BERT checkpoint a predictor starts from does not hold."""
+    skip = ("CoVe", "ELMo", "AllenELMo", "Bert")
+    drop = ("eval_embed.weight", "fixed_embedding_fast", "fixed_embedding_glove")
+    keep = set(k for k in trained if k.startswith("Bert.bert_model.")) if "bert_train_layers" in opt else set()
+    return [k for k in keys if (not k.startswith(skip) and k not in drop) or k in keep]
+
+
 class SDNetTrainer(BaseTrainer):
     def __init__(self, opt, device=None, process_group=None):
         super().__init__(opt)
@@ -354,9 +365,12 @@ class SDNetTrainer(BaseTrainer):
 
     def _step_stream(self):
         """The step stream of the network's CURRENT mode (created on first use; one per priority: the process keeps the streams it
-        starts with, profiles/HISTORY.md round 5 (6b) / (9)); None on the CPU and with a trainable encoder (nothing runs ahead there)."""
+        starts with, profiles/HISTORY.md round 5 (6b) / (9)); None on the CPU and with a trainable encoder none of whose layers run ahead."""
         dev = self.device
-        unlocked = getattr(getattr(self.network, "Bert", None), "bert_model", None) is not None
+        bert = getattr(self.network, "Bert", None)
+        unlocked = getattr(bert, "bert_model", None) is not None
+        if unlocked and bert.runs_ahead():
+            unlocked = False                # opt['bert_train_layers']: the frozen lower layers run ahead as the frozen encoder does
         if dev.type != "cuda" or unlocked:
             return None
         pr = self.network.trunk_stream_priority()       # (differs between training and evaluation in the fp16c schedule)
@@ -728,10 +742,11 @@ class SDNetTrainer(BaseTrainer):
     def save_for_predict(self, filename):
         """:492-509 - network weights without BERT / fixed embeddings, plus the config."""
         self.flush_readback()
-        skip = ("CoVe", "ELMo", "AllenELMo", "Bert")
-        state = {k: v for k, v in self.network.state_dict().items() if not k.startswith(skip)}
-        for k in ("eval_embed.weight", "fixed_embedding_fast", "fixed_embedding_glove"):
-            state.pop(k, None)
+        full = self.network.state_dict()
+        # (of the encoder, only tensors its passes use: the checkpoint's pooler head is a parameter too and never gets a gradient)
+        used = set("Bert.bert_model." + n for n in getattr(getattr(getattr(self.network, "Bert", None), "bert_model", None), "_order", ()))
+        trained = [n for n, p in self.network.named_parameters() if p.requires_grad and (not n.startswith("Bert.bert_model.") or n in used)]
+        state = {k: full[k] for k in predict_checkpoint_keys(full, self.opt, trained)}
         cfg = {k: v for k, v in self.opt.items() if isinstance(v, (int, float, str, bool))}
         try:
             torch.save({"state_dict": {"network": state}, "config": cfg}, filename)
