@@ -1394,3 +1394,91 @@ def test_gelu_bwd_rows(M, N):
     assert maxerr(dd.float(), dref) < 2.0 ** -8 * float(dref.abs().max()) + 1e-6
     pref = dref.view(M // 128, 128, N).sum(1)
     assert maxerr(part, pref) < 2e-5 * 128 ** 0.5 + 1e-4 * float(pref.abs().max())
+
+
+# ---------------------------------------------------------------------------------------------------------
+def _scorer_ref(x, u1, u2, uh, w, b, mask, ES, mask_flag):
+    """float64 restatement of the fused answer scorer (Models/Layers.py:352-432, useES + no_answer):
+    probs = softmax([x_i . u(i) (-inf where masked, if mask_flag), w . (softmax(mask(x . uh)) . x) + b]), u(i) = u2 for i < ES else u1"""
+    L = x.shape[1]
+    first = (torch.arange(L) < ES).view(1, L, 1)
+    s = (x * torch.where(first, u2.unsqueeze(1), u1.unsqueeze(1))).sum(-1)
+    if mask_flag:
+        s = s.masked_fill(mask.eq(0), float("-inf"))
+    a = torch.softmax((x * uh.unsqueeze(1)).sum(-1).masked_fill(mask.eq(0), float("-inf")), 1)
+    na = (a.unsqueeze(1) @ x).squeeze(1) @ w.view(-1) + b
+    return torch.softmax(torch.cat([s, na.unsqueeze(1)], 1), 1)
+
+
+def _scorer_inputs(B, L, D, ES, g):
+    x = torch.randn(B, L, D, generator=g)
+    u1, u2, uh = (torch.randn(B, D, generator=g) / D ** 0.5 for _ in range(3))          # scores of O(1)
+    w, b = torch.randn(D, generator=g) / D ** 0.5, torch.randn(1, generator=g)
+    mask = (torch.rand(B, L, generator=g) < 0.8).to(torch.uint8)                        # holes everywhere, inside the first ES slots too
+    for i in range(B):
+        mask[i, int(torch.randint(1, L + 1, (1,), generator=g)):] = 0                   # ragged tails
+        mask[i, int(torch.randint(0, L, (1,), generator=g))] = 1                        # at least one live slot
+    return x, u1, u2, uh, w, b, mask
+
+
+@pytest.mark.parametrize("B,L,D,ES,mask_flag", [(1, 1, 4, 0, 1), (3, 2, 4, 1, 1), (2, 136, 500, 36, 1), (2, 257, 260, 1, 0), (2, 1024, 8, 1023, 1),
+                                                (1, 1000, 1028, 500, 1), (4, 37, 252, 37, 0)])
+def test_fused_scorer_shapes(B, L, D, ES, mask_flag):
+    """ops.fused_scorer (ruart_scorer_fwd / _bwd, csrc/sdnet_scorer.hip) against float64 autograd of the same expression: the
+    probabilities and the gradients of x, u1, u2, uh, w and b, at the bounds of the sibling fp32 kernels (test_fused_attention_shapes).
+    Shapes: one slot; ES = 0, 1, L - 1 and L; L beyond one pass of the 256 threads and at the 1024 maximum; D below one wave's
+    float4 stride (8), not a multiple of it (260, 500) and beyond a block's (1028); with and without the -inf of mask_flag.
+    Measured: probabilities within 2.5e-8, gradients within 2.9e-7 of max(1, |ref|)."""
+    from ruart_amd import ops
+    d = dev()
+    g = torch.Generator().manual_seed(B * 1000 + L + D)
+    ins = _scorer_inputs(B, L, D, ES, g)
+    mask = ins[6]
+    gp = torch.randn(B, L + 1, generator=g)
+    leaves = [t.double().requires_grad_() for t in ins[:6]]
+    ref = _scorer_ref(*leaves, mask, ES, mask_flag)
+    (ref * gp.double()).sum().backward()
+
+    def run():
+        dl = [t.to(d).requires_grad_() for t in ins[:6]]
+        probs = ops.fused_scorer(*dl, mask.to(d), ES, bool(mask_flag))
+        (probs * gp.to(d)).sum().backward()
+        return [probs.detach()] + [t.grad for t in dl]
+
+    ops.nan_flag.check_and_clear()
+    got = run()
+    ops.nan_flag.check_and_clear()
+    e_p = maxerr(got[0], ref.detach()) / max(1.0, float(ref.abs().max()))
+    e_g = {n: maxerr(t, r.grad) / max(1.0, float(r.grad.abs().max())) for n, t, r in zip(("gx", "gu1", "gu2", "guh", "gw", "gb"), got[1:], leaves)}
+    print("fused scorer (%d, %d, %d, ES %d, flag %d): probs %.2e; %s" % (B, L, D, ES, mask_flag, e_p, ", ".join("%s %.2e" % kv for kv in e_g.items())))
+    assert e_p < 2e-5
+    assert max(e_g.values()) < 5e-5, e_g
+    assert all(torch.equal(a, b) for a, b in zip(got, run()))                  # every sum in a fixed order
+
+
+def test_fused_scorer_rejects_bad_sizes_and_flags_a_dead_sample():
+    """L beyond the kernel's 1024 slots, D % 4 != 0 and ES > L are refused at the C ABI; a sample whose slots are ALL masked has no
+    softmax - the reference asserts on the NaN (Models/Layers.py:430), here the device flag raises at the step's one check."""
+    from ruart_amd import ops
+    lib = hip.load()
+    d = dev()
+    B, L, D = 1, 1025, 6
+    x, probs, a = torch.zeros(B, L, D, device=d), torch.zeros(B, L + 1, device=d), torch.zeros(B, L, device=d)
+    u, w, b1, mask = torch.zeros(B, D, device=d), torch.zeros(D, device=d), torch.zeros(1, device=d), torch.ones(B, L, dtype=torch.uint8, device=d)
+    st = hip.stream_ptr()
+    assert lib.ruart_scorer_fwd(hip.ptr(x), hip.ptr(u), hip.ptr(u), hip.ptr(u), hip.ptr(w), hip.ptr(b1), hip.ptr(mask), hip.ptr(probs), hip.ptr(a),
+                                B, L, D, L + 1, 1, st) != 0
+    gx, gu, gb = torch.zeros_like(x), torch.zeros_like(u), torch.zeros(B, device=d)
+    assert lib.ruart_scorer_bwd(hip.ptr(x), hip.ptr(u), hip.ptr(u), hip.ptr(u), hip.ptr(w), hip.ptr(probs), hip.ptr(a), hip.ptr(probs), hip.ptr(gx),
+                                hip.ptr(gu), hip.ptr(gu), hip.ptr(gu), hip.ptr(gu), hip.ptr(gb), B, L, D, L + 1, st) != 0
+    g = torch.Generator().manual_seed(9)
+    x, u1, u2, uh, w, b, mask = _scorer_inputs(2, 20, 8, 5, g)
+    ops.nan_flag.check_and_clear()
+    ok = ops.fused_scorer(*[t.to(d) for t in (x, u1, u2, uh, w, b)], mask.to(d), 5, True)
+    ops.nan_flag.check_and_clear()                                             # live samples: nothing raised
+    assert torch.isfinite(ok).all()
+    mask[1] = 0
+    ops.fused_scorer(*[t.to(d) for t in (x, u1, u2, uh, w, b)], mask.to(d), 5, True)
+    with pytest.raises(AssertionError):
+        ops.nan_flag.check_and_clear()
+    ops.nan_flag.check_and_clear()                                             # ... and the flag is cleared again

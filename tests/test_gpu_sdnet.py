@@ -885,3 +885,61 @@ def test_deferred_weight_gradients_are_bitwise_the_same(golden):
     assert grads["site"].keys() == grads["grouped"].keys()
     bad = [n for n in grads["site"] if not torch.equal(grads["site"][n], grads["grouped"][n])]
     assert not bad, bad[:5]
+
+
+def test_fused_scorer_equals_the_elementwise_form_with_variational_dropout():
+    """GetFinalScores in training mode with VARIATIONAL dropout (p = 0.3): the fused form folds the (B, D) masks of x into u1 / u2 and
+    draws them - and the element-wise dropouts of h0 between them - in the order the op-by-op form does.  From the same generator state
+    and an unfilled MaskBank both forms must give the same probabilities and the same gradients of x, h0 and every parameter, at the
+    fp32 kernels' bounds (2e-5 / 5e-5 of max(1, |ref|)); a mask drawn out of order or applied to the wrong vector moves them by O(1).
+    Slots are masked inside the ES range and in a ragged tail.  Measured: probabilities 7.2e-7, gradients 5.4e-6 (attn.linear.weight)."""
+    import ruart_amd.layers as L
+    from ruart_amd import ops
+    d = "cuda:0"
+    g = torch.Generator().manual_seed(17)
+    B, Ls, D, Hh, ES = 3, 41, 252, 250, 9
+    ga = L.GetFinalScores(D, Hh, yesno=False, no_answer=True, useES=True)
+    with torch.no_grad():
+        for prm in ga.parameters():
+            prm.copy_(torch.randn(prm.shape, generator=g) / max(prm.shape[-1], 1) ** 0.5)
+    ga = ga.to(d).train()
+    x0, h00 = torch.randn(B, Ls, D, generator=g), torch.randn(B, Hh, generator=g)
+    mask = (torch.rand(B, Ls, generator=g) < 0.8).float()
+    mask[0, 30:], mask[1, 12:], mask[:, 3], mask[2, 1] = 0, 0, 1, 0
+    gp = torch.randn(B, Ls + 1, generator=g).to(d)
+    calls = []
+    orig = ga._forward_fused
+    ga._forward_fused = lambda *a, **k: (calls.append(1), orig(*a, **k))[1]
+    saved = (L.do_seq_dropout, L.dropout_p, L.fused_scorer_enabled, L.mask_bank, ops.trunk_gemm)
+
+    def run(fused):
+        L.fused_scorer_enabled = fused
+        L.mask_bank = L.MaskBank()                           # unfilled: every site draws its own mask from the generator
+        torch.manual_seed(5)
+        ga.zero_grad(set_to_none=True)
+        x, h0 = x0.to(d).requires_grad_(), h00.to(d).requires_grad_()
+        probs = ga(x, h0, mask.to(d), ES, mask_flag=True)
+        (probs * gp).sum().backward()
+        ops.nan_flag.check_and_clear()
+        return probs.detach(), {"x": x.grad, "h0": h0.grad, **{n: p.grad.clone() for n, p in ga.named_parameters() if p.grad is not None}}
+
+    try:
+        L.set_dropout_prob(0.3)
+        L.set_seq_dropout(True)
+        ops.trunk_gemm = "x3"
+        p_ref, g_ref = run(False)
+        assert not calls
+        p_fus, g_fus = run(True)
+        assert len(calls) == 1
+    finally:
+        L.do_seq_dropout, L.dropout_p, L.fused_scorer_enabled, L.mask_bank, ops.trunk_gemm = saved
+        ga._forward_fused = orig
+    assert g_ref.keys() == g_fus.keys() and {"x", "h0", "attn.linear.weight", "attn2.linear.bias", "noanswer_linear.weight", "noanswer_w.weight",
+                                             "noanswer_w.bias"} <= set(g_ref)
+    e_p = float((p_fus - p_ref).abs().max()) / max(1.0, float(p_ref.abs().max()))
+    e_g = {n: float((g_fus[n] - g_ref[n]).abs().max()) / max(1.0, float(g_ref[n].abs().max())) for n in g_ref}
+    worst = max(e_g, key=e_g.get)
+    print("fused scorer vs op-by-op, dropout 0.3: probs %.2e, gradients <= %.2e (%s)" % (e_p, e_g[worst], worst))
+    assert float((p_ref[:, :-1][mask.to(d) == 0]).abs().max()) == 0.0 and float(g_ref["x"].abs().max()) > 0
+    assert e_p < 2e-5
+    assert e_g[worst] < 5e-5, e_g

@@ -321,7 +321,8 @@ def test_attention_train_fwd_bwd_vs_autograd():
 
 def test_attention_train_dropout_is_consistent():
     """With probability dropout the output is linear in V for a fixed mask: <dO, O> == <dV, V> holds exactly when the backward
-    regenerates the forward's mask; the share of dropped probabilities is p."""
+    regenerates the forward's mask in dV.  The identity says nothing about dQ or dK, nor about the share of dropped probabilities:
+    test_attention_dropout_vs_float64_with_the_recovered_mask and test_attention_dropout_mask_properties below hold those."""
     lib = hip.load()
     g = torch.Generator().manual_seed(12)
     heads, p = 2, 0.1
@@ -508,3 +509,178 @@ def test_trainable_encoder_long_sequence_stays_off_the_vendor_gemm():
     x = ln(lin(h, "output.dense") + x, pre + "output.LayerNorm")
     ref = torch.cat([x[0], x[1, :390]], 0)
     assert float((out[0].double().cpu() - ref).abs().max()) < 2e-4
+
+
+# ---- attention-probability dropout against float64 with the kernel's own mask -------------------------------------------------------
+from tests import _dropout_probe as PB          # noqa: E402
+from tests import _dropout_ref as R             # noqa: E402
+
+_DROP_SEED = 0x2F6E2B1
+_recovered_cache = {}
+
+
+def _recovered(lib, family, p, seed=_DROP_SEED):
+    """the (family, p, seed) cell's plan and the masks recovered from the forward kernels (computed once per module run; read-only)"""
+    key = (family, p, seed)
+    if key not in _recovered_cache:
+        lens, heads = R.ATTN_FAMILIES[family]
+        cu, win, ch, tok_lo = _long_plan(lens)
+        masks, dev = PB.attn_masks(lib, heads, cu, win, ch, tok_lo, p, seed)
+        _recovered_cache[key] = (cu, win, ch, tok_lo, masks, dev)
+    return _recovered_cache[key]
+
+
+def _attn_drop_run(lib, qd, dOd, heads, win, ch, tok_lo, p, seed):
+    """forward + backward through the window kernels and, where the plan has chunks, the *_long kernels:
+    (context rows, [dQ | dK | dV] rows, [query | value] bias sums)"""
+    T, H = qd.shape[0], heads * 64
+    nw, nc = win[0].numel(), ch[0].numel()
+    ctx = PB.attn_fwd(lib, qd, heads, win, ch, tok_lo, p, seed)
+    dqkv = torch.zeros(T, 3 * H, dtype=torch.bfloat16, device=DEV)
+    bw = torch.zeros(max(nw, 1), 2 * H, device=DEV)
+    bl = torch.zeros(max(nc, 1), 2 * H, device=DEV)
+    if nw:
+        assert lib.ruart_attn_train_bwd(hip.ptr(qd), 3 * H, hip.ptr(dOd), H, hip.ptr(dqkv), 3 * H, H, heads, nw, hip.ptr(win[0]), hip.ptr(win[1]),
+                                        hip.ptr(tok_lo), p, seed, hip.ptr(bw), _st()) == 0
+    if nc:
+        lse = torch.empty(T, heads, device=DEV)
+        ctx2 = torch.empty_like(ctx)
+        assert lib.ruart_attn_train_fwd_long(hip.ptr(qd), 3 * H, hip.ptr(ctx2), H, H, heads, nc, hip.ptr(ch[0]), hip.ptr(ch[1]), hip.ptr(ch[2]),
+                                             hip.ptr(ch[3]), p, seed, hip.ptr(lse), _st()) == 0
+        delta = torch.empty(T, heads, device=DEV)
+        scale = torch.empty(nc, heads, device=DEV)
+        assert lib.ruart_attn_train_bwd_long(hip.ptr(qd), 3 * H, hip.ptr(dOd), H, hip.ptr(dqkv), 3 * H, H, heads, nc, hip.ptr(ch[0]),
+                                             hip.ptr(ch[1]), hip.ptr(ch[2]), hip.ptr(ch[3]), hip.ptr(ch[4]), p, seed, hip.ptr(lse), hip.ptr(delta),
+                                             hip.ptr(scale), hip.ptr(bl), _st()) == 0
+    torch.cuda.synchronize()
+    return ctx, dqkv, bw.double().sum(0) + bl.double().sum(0)
+
+
+@pytest.mark.parametrize("p", [0.1, 0.5])
+@pytest.mark.parametrize("family", list(R.ATTN_FAMILIES))
+def test_attention_dropout_vs_float64_with_the_recovered_mask(family, p):
+    """Probability dropout ON (0.1: what ships; 0.5: where a mishandled multiplier weighs most), window kernels and *_long kernels:
+    the mask M is recovered from the forward kernel itself (tests/_dropout_probe.py), then context rows, [dQ | dK | dV] rows and the
+    query / value bias sums are held, per sequence, to a float64 autograd of O = (softmax(Q K^T) o M) V - at the bounds the p = 0 tests
+    above hold (context 4e-3; gradients max-rel 4e-2 and rel-L2 1.5e-2 per sequence and block; bias sums 2e-3 of the column abs-sum).
+    A one-token sequence has dQ = dK = 0 exactly; its rows are measured on the scale of the whole stream's block.
+    tests/test_dropout_ref.py shows that a delta or a dS without D, another head's mask or a transposed one miss these bounds by > 3x.
+    Measured (MI355X, profiles/dropout_gradient_tests.txt), worst of the four cells: recovered multipliers within 4.4e-4 of 1 / (n (1 - p)),
+    context 3.4e-3, bias sums 4.7e-5, max-rel 4.0e-3, rel-L2 1.74e-3 - the same as at p = 0."""
+    lib = hip.load()
+    lens, heads, cu0, qkv, dO = R.attention_inputs(family)
+    H = heads * 64
+    cu, win, ch, tok_lo, masks, dev = _recovered(lib, family, p)
+    assert np.array_equal(cu, cu0)
+    ctx, dqkv, bsum = _attn_drop_run(lib, qkv.half().to(DEV), dO.bfloat16().to(DEV), heads, win, ch, tok_lo, p, _DROP_SEED)
+    ref, want = R.attention_grads(qkv, dO, cu, heads, masks, plain=True)
+    got, bsum = dqkv.double().cpu(), bsum.cpu()
+    f_err = float((ctx.double().cpu() - ref).abs().max())
+    b_err = max(float((bs - want[:, sl].sum(0)).abs().max()) / float(want[:, sl].abs().sum(0).max())
+                for sl, bs in ((slice(0, H), bsum[:H]), (slice(2 * H, 3 * H), bsum[H:])))
+    worst = {}
+    for name, sl in (("dQ", slice(0, H)), ("dK", slice(H, 2 * H)), ("dV", slice(2 * H, 3 * H))):
+        whole = float(want[:, sl].abs().max())
+        for a, b in zip(cu[:-1], cu[1:]):
+            w_, g_ = want[a:b, sl], got[a:b, sl]
+            if float(w_.abs().max()) == 0.0:
+                e, rel = float((g_ - w_).abs().max()) / whole, 0.0
+            else:
+                e, rel = R.block_errors(g_, w_)
+            worst[name] = max(worst.get(name, (0.0, 0.0, 0)), (e, rel, int(b - a)))
+    print("attention dropout %-6s p=%.1f: mask entries off by <= %.2e; ctx %.2e; bias sums %.2e; %s"
+          % (family, p, dev, f_err, b_err, "; ".join("%s max-rel %.2e rel-L2 %.2e (len %d)" % ((k,) + v) for k, v in worst.items())))
+    assert f_err < 4e-3                                                              # f16 operands / output, O(1) values
+    assert b_err < 2e-3
+    for name, sl in (("dQ", slice(0, H)), ("dK", slice(H, 2 * H)), ("dV", slice(2 * H, 3 * H))):
+        whole = float(want[:, sl].abs().max())
+        for a, b in zip(cu[:-1], cu[1:]):
+            w_, g_ = want[a:b, sl], got[a:b, sl]
+            if float(w_.abs().max()) == 0.0:
+                assert float((g_ - w_).abs().max()) < R.ATTN_BOUNDS[0] * whole, (name, int(b - a))
+                continue
+            e, rel = R.block_errors(g_, w_)
+            assert e < R.ATTN_BOUNDS[0] and rel < R.ATTN_BOUNDS[1], (name, int(b - a), e, rel)      # bf16 results, f16 operands
+
+
+def test_attention_dropout_mask_properties():
+    """The recovered masks are Bernoulli(1 - p) streams that differ where they must: the kept share is 1 - p overall and per head; two
+    heads, two sequences of equal length and two seeds each agree at p^2 + (1-p)^2 - as independent streams do -, not at 1 (one mask
+    for all heads / all sequences / all seeds), every one within 5 sigma; the streams of two heads (seeds h * 0x9E3779B1 apart) are no
+    translated copies of each other (shifts 0, +-1, +-one query row); and the window and the *_long kernels give the same entries for
+    the same (query token, key offset).  Measured: kept share within 2.2 sigma, pair agreement 2.3 sigma, shifted head streams 1.1 sigma."""
+    lib = hip.load()
+    worst_keep = worst_pair = 0.0
+    for family in R.ATTN_FAMILIES:
+        lens, heads = R.ATTN_FAMILIES[family]
+        for p in (0.1, 0.5):
+            masks = _recovered(lib, family, p)[4]
+            keep = [m > 0 for m in masks]
+            flat = lambda ks, h: torch.cat([k[h].reshape(-1) for k in ks])
+            sig = [R.keep_sigmas(torch.cat([k.reshape(-1) for k in keep]), p)] + [R.keep_sigmas(flat(keep, h), p) for h in range(heads)]
+            worst_keep = max(worst_keep, max(sig))
+            assert max(sig) < 5, (family, p, sig)
+            for h in range(heads):
+                for h2 in range(h + 1, heads):
+                    s = R.agree_sigmas(flat(keep, h), flat(keep, h2), p)
+                    worst_pair = max(worst_pair, s)
+                    assert s < 5, ("heads", family, p, h, h2, s)
+            for i in range(len(lens)):                                       # sequences of equal length (other query tokens)
+                for j in range(i + 1, len(lens)):
+                    if lens[i] == lens[j] and lens[i] >= 30:
+                        s = R.agree_sigmas(keep[i], keep[j], p)
+                        worst_pair = max(worst_pair, s)
+                        assert s < 5, ("sequences", family, p, i, j, s)
+            if p == 0.1:
+                other = [m > 0 for m in _recovered(lib, family, p, _DROP_SEED + 1)[4]]
+                s = R.agree_sigmas(torch.cat([k.reshape(-1) for k in keep]), torch.cat([k.reshape(-1) for k in other]), p)
+                worst_pair = max(worst_pair, s)
+                assert s < 5, ("seeds", family, s)
+    # the two heads' streams of the 512-token sequence, in index order (query row major): no translated copy
+    keep = _recovered(lib, "long", 0.1)[4][5] > 0
+    n = keep.shape[1]
+    worst_shift = 0.0
+    for d in (0, 1, -1, n, -n):
+        s = R.shifted_agree_sigmas(keep[0].reshape(-1), keep[1].reshape(-1), d, 0.1)
+        worst_shift = max(worst_shift, s)
+        assert s < 5, ("head streams", d, s)
+    # one stream for both kernel families: sequences of 64, 50 and 7 tokens as windows, then each as a chunk of itself
+    cu = np.array([0, 64, 114, 121])
+    to = lambda a: torch.tensor(a, dtype=torch.int32, device=DEV)
+    tok_lo = torch.from_numpy(np.repeat(cu[:-1], np.diff(cu)).astype(np.int32)).to(DEV)
+    m_win, _ = PB.attn_masks(lib, 2, cu, [to([0, 64]), to([64, 121])], None, tok_lo, 0.1, _DROP_SEED)
+    m_long, _ = PB.attn_masks(lib, 2, cu, [to([]), to([])], [to([0, 64, 114]), to([64, 114, 121]), to([0, 64, 114]), to([64, 114, 121]), to([0, 1, 2])],
+                              tok_lo, 0.1, _DROP_SEED)
+    assert all(torch.equal(a, b) for a, b in zip(m_win, m_long))
+    assert float((m_win[0] > 0).double().mean()) < 0.95                       # ... and it is a mask
+    print("attention masks: kept share off by <= %.2f sigma, pair agreement by <= %.2f sigma, shifted head streams by <= %.2f sigma"
+          % (worst_keep, worst_pair, worst_shift))
+
+
+def test_dropout_streams_of_the_encoder_are_unrelated():
+    """The streams the encoder really draws - a pass's seed s, its sites s + 7919 k (bert_train16._Run._seed: k = 1 .. 12 covers three
+    layers), another rank's s + 0x632BE5AB - taken from the LayerNorm kernel at R = 300, H = 768, p = 0.1: for every pair and every
+    shift d in {0, +-1, +-H, +-(seed_B - seed_A), +-2 (seed_B - seed_A)} that is in range, mask_A[i + d] agrees with mask_B[i] at
+    p^2 + (1-p)^2 = 0.82 within 5 sigma of the overlap.  A hash keyed by ONE addition of the seed to the index makes mask_B a
+    translated copy of mask_A (agreement 1 at d = seed_B - seed_A): the defect csrc/common.h's drop_scale was rewritten to remove.
+    Measured: 767 (pair, shift) cells, the worst 2.5 sigma off."""
+    lib = hip.load()
+    R_, H, p, s0 = 300, 768, 0.1, 0x1B2E3D47
+    seeds = [s0] + [s0 + 7919 * k for k in range(1, 13)] + [s0 + 0x632BE5AB]
+    keep = [(PB.ln_mask(lib, R_, H, p, sd & 0x7FFFFFFF, 0) > 0).reshape(-1).to(DEV) for sd in seeds]
+    worst, worst_keep, n_checked = 0.0, 0.0, 0
+    for k in keep:
+        worst_keep = max(worst_keep, R.keep_sigmas(k, p))
+    assert worst_keep < 5
+    for i in range(len(seeds)):
+        for j in range(i + 1, len(seeds)):
+            dd = seeds[j] - seeds[i]
+            for d in sorted({0, 1, -1, H, -H, dd, -dd, 2 * dd, -2 * dd}):
+                s = R.shifted_agree_sigmas(keep[i], keep[j], d, p)
+                if s is None:
+                    continue
+                n_checked += 1
+                worst = max(worst, s)
+                assert s < 5, (i, j, d, s)
+    assert n_checked >= 91 * 5 + 78 * 2            # every pair at 0, +-1, +-H; the site pairs at +-(seed difference) at least
+    print("encoder dropout streams: %d (pair, shift) cells, agreement off by <= %.2f sigma, kept share by <= %.2f sigma" % (n_checked, worst, worst_keep))
