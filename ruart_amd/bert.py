@@ -462,7 +462,7 @@ class _Buffers:
         self.stats = None
 
     def get(self, w, Tp):
-        lib = hip.load()
+        lib = hip.kernels()
         es = 4 if w.dtype == hip.DT_F32 else 2
         need_l = w.n_layers * Tp * w.hidden * es                      # bytes
         if self.layers is None or self.layers.numel() < need_l or self.layers.device != w.device:
@@ -487,7 +487,7 @@ _buffers = _Buffers()
 def bert_encode(weights, packed, buffers=None):
     """Run the encoder; returns all layer outputs as one (n_layers, Tp, H) tensor in the weights' dtype.
     The tensor aliases a reusable buffer: consume it before the next call."""
-    lib = hip.load()
+    lib = hip.kernels()
     if getattr(packed, "max_pos", 0) > weights.cfg["max_position_embeddings"]:
         raise ValueError("the packed stream addresses %d position embeddings, the checkpoint has %d"
                          % (packed.max_pos, weights.cfg["max_position_embeddings"]))
@@ -498,14 +498,10 @@ def bert_encode(weights, packed, buffers=None):
         # output LayerNorms' gamma / beta tables) what turns them into the layer outputs - on the fly in the pooling kernel
         # (_PoolMix), or materialised by layer_outputs() for tests
         stats = buffers.stats_for(weights, packed.Tp)
-        rc = lib.ruart_bert_forward_folded(ctypes.byref(weights.c_model), ctypes.byref(packed.c_batch), hip.ptr(layers), hip.ptr(stats),
-                                           hip.ptr(ws), ws_bytes, hip.stream_ptr())
-        hip.check(rc, "ruart_bert_forward_folded")
+        lib.ruart_bert_forward_folded(ctypes.byref(weights.c_model), ctypes.byref(packed.c_batch), layers, stats, ws, ws_bytes, hip.stream_ptr())
         layers._ln = (stats, weights.ln2_g_all, weights.ln2_b_all)
         return layers
-    rc = lib.ruart_bert_forward(ctypes.byref(weights.c_model), ctypes.byref(packed.c_batch), hip.ptr(layers), hip.ptr(ws),
-                                ws_bytes, hip.stream_ptr())
-    hip.check(rc, "ruart_bert_forward")
+    lib.ruart_bert_forward(ctypes.byref(weights.c_model), ctypes.byref(packed.c_batch), layers, ws, ws_bytes, hip.stream_ptr())
     return layers
 
 
@@ -533,27 +529,25 @@ class _PoolMix(torch.autograd.Function):
         """``span_start_last``: the spans' first rows in the LAST layer's matrix when the encoder left it compacted
         (PackedTokens.set_last_rows); None = as in every other layer.  ``ln_stats`` / ``ln_g`` / ``ln_b``: `layers` holds the
         pre-LayerNorm rows of a folded pass (bert_encode) and the kernel normalises what it reads."""
-        lib = hip.load()
+        lib = hip.kernels()
         NL, Tp, H = layers.shape
         W = span_start.numel()
         out = torch.zeros(n_rows, H, dtype=torch.float32, device=layers.device)
         lw = layer_w.detach().to(torch.float32).contiguous()
         if W > 0 and "pool" not in _ABL_SKIP:          # (timing diagnostics only, see ops._ABL_SKIP: empty in every product run)
             if ln_stats is not None:
-                rc = lib.ruart_bert_pool_mix_ln(hip.ptr(layers), Tp * H, H, NL, hip.ptr(ln_stats), Tp, hip.ptr(ln_g), hip.ptr(ln_b),
-                                                hip.ptr(span_start), hip.ptr(span_start_last), hip.ptr(span_len), hip.ptr(dst_row), hip.ptr(lw),
-                                                hip.ptr(out), H, W, H, hip.stream_ptr())
+                lib.ruart_bert_pool_mix_ln(layers, Tp * H, H, NL, ln_stats, Tp, ln_g, ln_b, span_start, span_start_last, span_len, dst_row, lw,
+                                           out, H, W, H, hip.stream_ptr())
             else:
-                rc = lib.ruart_bert_pool_mix(hip.ptr(layers), Tp * H, H, dtype_code, NL, hip.ptr(span_start), hip.ptr(span_start_last), hip.ptr(span_len),
-                                             hip.ptr(dst_row), hip.ptr(lw), hip.ptr(out), H, W, H, hip.stream_ptr())
-            hip.check(rc, "ruart_bert_pool_mix")
+                lib.ruart_bert_pool_mix(layers, Tp * H, H, dtype_code, NL, span_start, span_start_last, span_len, dst_row, lw, out, H, W, H,
+                                        hip.stream_ptr())
         ctx.save_for_backward(layers, span_start, span_len, dst_row, span_start_last, ln_stats, ln_g, ln_b)
         ctx.dtype_code = dtype_code
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
-        lib = hip.load()
+        lib = hip.kernels()
         layers, span_start, span_len, dst_row, span_start_last, ln_stats, ln_g, ln_b = ctx.saved_tensors
         NL, Tp, H = layers.shape
         W = span_start.numel()
@@ -562,14 +556,11 @@ class _PoolMix(torch.autograd.Function):
             grad_out = grad_out.contiguous()
             partial = torch.empty(W * NL, dtype=torch.float32, device=layers.device)
             if ln_stats is not None:
-                rc = lib.ruart_bert_pool_mix_ln_bwd(hip.ptr(layers), Tp * H, H, NL, hip.ptr(ln_stats), Tp, hip.ptr(ln_g), hip.ptr(ln_b),
-                                                    hip.ptr(span_start), hip.ptr(span_start_last), hip.ptr(span_len), hip.ptr(dst_row),
-                                                    hip.ptr(grad_out), H, hip.ptr(partial), hip.ptr(g), W, H, hip.stream_ptr())
+                lib.ruart_bert_pool_mix_ln_bwd(layers, Tp * H, H, NL, ln_stats, Tp, ln_g, ln_b, span_start, span_start_last, span_len, dst_row,
+                                               grad_out, H, partial, g, W, H, hip.stream_ptr())
             else:
-                rc = lib.ruart_bert_pool_mix_bwd(hip.ptr(layers), Tp * H, H, ctx.dtype_code, NL, hip.ptr(span_start), hip.ptr(span_start_last), hip.ptr(span_len),
-                                                 hip.ptr(dst_row), hip.ptr(grad_out), H, hip.ptr(partial), hip.ptr(g), W, H,
-                                                 hip.stream_ptr())
-            hip.check(rc, "ruart_bert_pool_mix_bwd")
+                lib.ruart_bert_pool_mix_bwd(layers, Tp * H, H, ctx.dtype_code, NL, span_start, span_start_last, span_len, dst_row, grad_out, H,
+                                            partial, g, W, H, hip.stream_ptr())
         return g, None, None, None, None, None, None, None, None, None, None
 
 

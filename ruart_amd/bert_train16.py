@@ -32,6 +32,8 @@ active dropout takes their outputs from the frozen path's fp16c pass (``bert.Ber
 step ahead), ``ruart_rows_ln_to_16`` hands them over as the first k planes of the f16 layer block, and the layers from k on run as
 above; nothing is saved below k.  Every backward pass ends with layer k: no dX product into layer k-1, no embedding backward.
 """
+import os
+
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -48,10 +50,6 @@ _EMB_TENSORS = ("embeddings.word_embeddings.weight", "embeddings.position_embedd
                 "embeddings.LayerNorm.gamma", "embeddings.LayerNorm.beta")
 
 
-def _chk(rc, what):
-    hip.check(rc, what)
-
-
 class _Run:
     """One forward / backward pass: buffers, launches and the saved activations."""
 
@@ -59,7 +57,7 @@ class _Run:
         self.m, self.packed, self.training = model, packed, training
         self.keep = keep                                              # False: a pass nobody will differentiate - nothing is saved
         self.P = dict(zip(model._order, params))
-        self.lib = hip.load()
+        self.lib = hip.kernels()
         self.dev = packed.ids.device
         self.T, self.Tp = packed.T, packed.Tp
         self.H, self.NL, self.nh = model.hidden, model.n_layers, model.n_heads
@@ -67,7 +65,6 @@ class _Run:
         self.I = int(model.cfg["intermediate_size"])
         self.p_h = model.p_hidden if training else 0.0
         self.p_a = model.p_attn if training else 0.0
-        import os
         self.fused_gelu_bwd = os.environ.get("RUART_FUSED_GELU_BWD") == "1"     # experiments: the GELU backward in the dX product's epilogue
         # one 31-bit stream id per pass (CPU generator: no device sync); every dropout site adds its own offset
         self.seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if (self.p_h > 0 or self.p_a > 0) else 0
@@ -91,8 +88,7 @@ class _Run:
         M, K = A.shape
         N = W.shape[0]
         out_dt = hip.DT_F32 if out.dtype == torch.float32 else in_dt
-        _chk(self.lib.ruart_gemm_16_nt(hip.ptr(A), K, hip.ptr(W), K, hip.ptr(bias), hip.ptr(res), N, res_dt, hip.ptr(out), N, out_dt, M, N, K, act,
-                                       in_dt, self._st()), "ruart_gemm_16_nt")
+        self.lib.ruart_gemm_16_nt(A, K, W, K, bias, res, N, res_dt, out, N, out_dt, M, N, K, act, in_dt, self._st())
         return out
 
     def _seed(self, layer, site):
@@ -102,8 +98,7 @@ class _Run:
         Tp, H = self.Tp, self.H
         y = self._new(Tp, H, torch.float16) if out is None else out
         pre, st = self._new(Tp, H, torch.float16), self._new(Tp, 2, torch.float32)
-        _chk(self.lib.ruart_ln_train_fwd(hip.ptr(x32), H, hip.ptr(res16), H, hip.ptr(g), hip.ptr(b), 1e-12, float(p), int(seed), post, hip.ptr(y),
-                                         hip.ptr(pre), hip.ptr(st), H, Tp, H, self._st()), "ruart_ln_train_fwd")
+        self.lib.ruart_ln_train_fwd(x32, H, res16, H, g, b, 1e-12, float(p), int(seed), post, y, pre, st, H, Tp, H, self._st())
         return y, pre, st
 
     def _prep_weights(self, l, scale):
@@ -130,7 +125,7 @@ class _Run:
             k += 1
             out.append(w16)
             back.append(wT)
-        _chk(self.lib.ruart_weight_prep_batch(items, 6, self._st()), "ruart_weight_prep_batch")      # the layer's six weights, one launch
+        self.lib.ruart_weight_prep_batch(items, 6, self._st())      # the layer's six weights, one launch
         self.wT[l] = back
         return out
 
@@ -149,21 +144,19 @@ class _Run:
         ctx = self._new(Tp, H, torch.float16, zero=True)
         plan = pk.train_plan(self.dev)
         if plan["n_win"]:                                            # windows of whole short sequences
-            _chk(lib.ruart_attn_train_fwd(hip.ptr(qkv), 3 * H, hip.ptr(ctx), H, H, self.nh, plan["n_win"], hip.ptr(plan["win"][0]),
-                                          hip.ptr(plan["win"][1]), hip.ptr(pk.tok_lo), float(self.p_a), self._seed(l, 0), st()), "ruart_attn_train_fwd")
+            lib.ruart_attn_train_fwd(qkv, 3 * H, ctx, H, H, self.nh, plan["n_win"], plan["win"][0], plan["win"][1], pk.tok_lo,
+                                     float(self.p_a), self._seed(l, 0), st())
         lse = None
         if plan["n_chunks"]:                                         # sequences longer than one window: <= 64-token chunks against the whole sequence
             c = plan["chunks"]
             lse = torch.empty(self.T, self.nh, dtype=torch.float32, device=self.dev)
-            _chk(lib.ruart_attn_train_fwd_long(hip.ptr(qkv), 3 * H, hip.ptr(ctx), H, H, self.nh, plan["n_chunks"], hip.ptr(c[0]), hip.ptr(c[1]),
-                                               hip.ptr(c[2]), hip.ptr(c[3]), float(self.p_a), self._seed(l, 0), hip.ptr(lse), st()),
-                 "ruart_attn_train_fwd_long")
+            lib.ruart_attn_train_fwd_long(qkv, 3 * H, ctx, H, H, self.nh, plan["n_chunks"], c[0], c[1], c[2], c[3], float(self.p_a),
+                                          self._seed(l, 0), lse, st())
         ao = self._gemm(ctx, wo16, P[pre + "attention.output.dense.bias"], self._new(Tp, H, torch.float32), hip.DT_F16)
         mid, pre1, st1 = self._ln_fwd(ao, x16, P[pre + "attention.output.LayerNorm.gamma"], P[pre + "attention.output.LayerNorm.beta"],
                                       self.p_h, self._seed(l, 1))
         h16, g16 = self._new(Tp, I, torch.float16), self._new(Tp, I, torch.float16)
-        _chk(lib.ruart_gemm_16_nt_gelu2(hip.ptr(mid), H, hip.ptr(w1_16), H, hip.ptr(P[pre + "intermediate.dense.bias"]), hip.ptr(h16), hip.ptr(g16),
-                                        I, Tp, I, H, hip.DT_F16, st()), "ruart_gemm_16_nt_gelu2")
+        lib.ruart_gemm_16_nt_gelu2(mid, H, w1_16, H, P[pre + "intermediate.dense.bias"], h16, g16, I, Tp, I, H, hip.DT_F16, st())
         ff = self._gemm(g16, w2_16, P[pre + "output.dense.bias"], ao, hip.DT_F16)           # reuses the fp32 buffer
         del g16
         _, pre2, st2 = self._ln_fwd(ff, mid, P[pre + "output.LayerNorm.gamma"], P[pre + "output.LayerNorm.beta"], self.p_h,
@@ -187,10 +180,9 @@ class _Run:
         ln = getattr(low, "_ln", None)
         if ln is not None:                  # folded pass: pre-LayerNorm fp32 rows + (mu, rstd) + the output LayerNorms' tables
             stats, g, b = ln
-            _chk(lib.ruart_rows_ln_to_16(hip.ptr(low), Tp * H, H, hip.ptr(stats), Tp, hip.ptr(g), hip.ptr(b), hip.ptr(self.layers), Tp * H, H, k,
-                                         T, Tp, H, self._st()), "ruart_rows_ln_to_16")
+            lib.ruart_rows_ln_to_16(low, Tp * H, H, stats, Tp, g, b, self.layers, Tp * H, H, k, T, Tp, H, self._st())
         elif low.dtype == torch.float32:    # unfolded fp16c pass (opt['bert_ln_fold'] = 0, a tail split): finished fp32 rows, pad rows zero
-            _chk(lib.ruart_cast_f32_to_16(hip.ptr(low), hip.ptr(self.layers), hip.DT_F16, k * Tp * H, 1.0, self._st()), "ruart_cast_f32_to_16")
+            lib.ruart_cast_f32_to_16(low, self.layers, hip.DT_F16, k * Tp * H, 1.0, self._st())
         else:
             raise ValueError("opt['bert_train_layers']: the frozen lower layers run in the fp16c precision")
         return self.layers[k - 1]
@@ -208,7 +200,7 @@ class _Run:
         bufs = self.m.__dict__.setdefault("_acc_buffers", _Buffers())
         layers32 = bert_encode(W, self.packed, bufs)                    # (NL, Tp, H) fp32; aliases a reusable buffer: consumed below
         self.layers = torch.empty(NL, Tp, H, dtype=torch.float16, device=self.dev)
-        _chk(lib.ruart_cast_f32_to_16(hip.ptr(layers32), hip.ptr(self.layers), hip.DT_F16, NL * Tp * H, 1.0, self._st()), "ruart_cast_f32_to_16")
+        lib.ruart_cast_f32_to_16(layers32, self.layers, hip.DT_F16, NL * Tp * H, 1.0, self._st())
         self.recompute = True
         self.saved, self.wT = {}, {}
         if layer_w is None:
@@ -243,14 +235,14 @@ class _Run:
             return self.layers                                        # frozen-encoder use: every layer output, no mix
         self.lw = layer_w.detach().to(torch.float32).contiguous()
         mixed = torch.empty(Tp, H, dtype=torch.float32, device=self.dev)
-        _chk(lib.ruart_mix_rows(hip.ptr(self.layers), Tp * H, H, NL, hip.ptr(self.lw), hip.ptr(mixed), H, Tp, H, st()), "ruart_mix_rows")
+        lib.ruart_mix_rows(self.layers, Tp * H, H, NL, self.lw, mixed, H, Tp, H, st())
         return mixed[:T]
 
     # -- backward ------------------------------------------------------------------------------------------------------------
     def _bf16(self, x16):
         """bf16 copy of a saved f16 activation (the X operand of a weight-gradient product; transient)"""
         out = self.xb[:x16.numel()].view(x16.shape)
-        _chk(self.lib.ruart_f16_to_bf16(hip.ptr(x16), hip.ptr(out), x16.numel(), self._st()), "ruart_f16_to_bf16")
+        self.lib.ruart_f16_to_bf16(x16, out, x16.numel(), self._st())
         return out
 
     def _dw(self, dY_bf16, X_bf16, row_scales=None):
@@ -265,13 +257,11 @@ class _Run:
         tchunk = ((Tp + nz - 1) // nz + 127) // 128 * 128
         nz = (Tp + tchunk - 1) // tchunk
         part = self.part[:nz * M * N]
-        _chk(lib.ruart_gemm_16_tn_splitk(hip.ptr(dY_bf16), M, hip.ptr(X_bf16), N, hip.ptr(part), N, M, N, Tp, tchunk, hip.DT_BF16, self._st()),
-             "ruart_gemm_16_tn_splitk")
+        lib.ruart_gemm_16_tn_splitk(dY_bf16, M, X_bf16, N, part, N, M, N, Tp, tchunk, hip.DT_BF16, self._st())
         outs, r0 = [], 0
         for rows, scale in (row_scales or [(M, 1.0)]):
             dW = torch.empty(rows, N, dtype=torch.float32, device=self.dev)
-            _chk(lib.ruart_splitk_reduce(hip.ptr(part[r0 * N:]), M * N, nz, hip.ptr(dW), rows * N, float(scale), 0, self._st()),
-                 "ruart_splitk_reduce")
+            lib.ruart_splitk_reduce(part[r0 * N:], M * N, nz, dW, rows * N, float(scale), 0, self._st())
             outs.append(dW)
             r0 += rows
         return outs if row_scales else outs[0]
@@ -287,9 +277,8 @@ class _Run:
         d_gemm = self._d_gemm if not post else None
         dg, db = torch.empty(H, device=self.dev), torch.empty(H, device=self.dev)
         dbias = torch.empty(H, device=self.dev) if not post else None
-        _chk(self.lib.ruart_ln_train_bwd(hip.ptr(dy), H, hip.ptr(add), hip.ptr(add_scale), hip.ptr(pre16), H, hip.ptr(stats), hip.ptr(gamma), float(p),
-                                         int(seed), post, hip.ptr(d_res), H, hip.ptr(d_gemm), H, hip.ptr(dg), hip.ptr(db), hip.ptr(dbias), 0,
-                                         hip.ptr(self.ln_ws), self.T, H, self._st()), "ruart_ln_train_bwd")
+        self.lib.ruart_ln_train_bwd(dy, H, add, add_scale, pre16, H, stats, gamma, float(p), int(seed), post, d_res, H, d_gemm, H, dg, db,
+                                    dbias, 0, self.ln_ws, self.T, H, self._st())
         return d_res, d_gemm, dg, db, dbias
 
     def backward(self, g_mixed):
@@ -303,7 +292,7 @@ class _Run:
         G[:T] = g_mixed
         d_lw = torch.empty(NL, dtype=torch.float32, device=dev)
         ws = torch.empty(512 * NL, dtype=torch.float32, device=dev)
-        _chk(lib.ruart_mix_rows_bwd(hip.ptr(self.layers), Tp * H, H, NL, hip.ptr(G), H, hip.ptr(d_lw), hip.ptr(ws), Tp, H, st()), "ruart_mix_rows_bwd")
+        lib.ruart_mix_rows_bwd(self.layers, Tp * H, H, NL, G, H, d_lw, ws, Tp, H, st())
         wmax = max(3 * H, I)
         self.xb = torch.empty(Tp * H, dtype=torch.bfloat16, device=dev)
         self.part = torch.empty(max(256, Tp // 128) * 256 * 256 + 4 * wmax * H, dtype=torch.float32, device=dev)
@@ -341,12 +330,11 @@ class _Run:
             d_h, g_b = self._new(Tp, I, torch.bfloat16), self._new(Tp, I, torch.bfloat16)
             db1_ff = torch.empty(I, dtype=torch.float32, device=dev)
             if self.fused_gelu_bwd:
-                _chk(lib.ruart_gemm_16_nt_gelu_bwd(hip.ptr(d_g2), H, hip.ptr(w2t), H, hip.ptr(h16), I, hip.ptr(d_h), hip.ptr(g_b), I,
-                                                   hip.ptr(self.cs_ws), Tp, I, H, st()), "ruart_gemm_16_nt_gelu_bwd")
+                lib.ruart_gemm_16_nt_gelu_bwd(d_g2, H, w2t, H, h16, I, d_h, g_b, I, self.cs_ws, Tp, I, H, st())
             else:      # (default, round 5) the plain product, then one elementwise pass: 160 + 190 us against 476 in the fused epilogue
                 self._gemm(d_g2, w2t, None, d_h, hip.DT_BF16)
-                _chk(lib.ruart_gelu_bwd_rows(hip.ptr(d_h), hip.ptr(h16), I, hip.ptr(g_b), hip.ptr(self.cs_ws), Tp, I, st()), "ruart_gelu_bwd_rows")
-            _chk(lib.ruart_colsum_f32_rows(hip.ptr(self.cs_ws), Tp // 128, I, I, hip.ptr(db1_ff), 0, st()), "ruart_colsum_f32_rows")
+                lib.ruart_gelu_bwd_rows(d_h, h16, I, g_b, self.cs_ws, Tp, I, st())
+            lib.ruart_colsum_f32_rows(self.cs_ws, Tp // 128, I, I, db1_ff, 0, st())
             grads[pre + "output.dense.weight"] = self._dw(d_g2, g_b)
             del g_b
             grads[pre + "intermediate.dense.bias"] = db1_ff
@@ -362,18 +350,15 @@ class _Run:
             d_ctx = self._gemm(d_g1, wot, None, self._new(Tp, H, torch.bfloat16), hip.DT_BF16)
             db = torch.empty(2 * H, dtype=torch.float32, device=dev)          # [query | value] bias gradients: the windows' sums, in order
             if n_win:
-                _chk(lib.ruart_attn_train_bwd(hip.ptr(qkv), 3 * H, hip.ptr(d_ctx), H, hip.ptr(dqkv), 3 * H, H, self.nh, n_win, hip.ptr(blk_q0),
-                                              hip.ptr(blk_q1), hip.ptr(pk.tok_lo), float(self.p_a), self._seed(l, 0), hip.ptr(self.bias_part), st()),
-                     "ruart_attn_train_bwd")
-                _chk(lib.ruart_colsum_f32_rows(hip.ptr(self.bias_part), n_win, 2 * H, 2 * H, hip.ptr(db), 0, st()), "ruart_colsum_f32_rows")
+                lib.ruart_attn_train_bwd(qkv, 3 * H, d_ctx, H, dqkv, 3 * H, H, self.nh, n_win, blk_q0, blk_q1, pk.tok_lo, float(self.p_a),
+                                         self._seed(l, 0), self.bias_part, st())
+                lib.ruart_colsum_f32_rows(self.bias_part, n_win, 2 * H, 2 * H, db, 0, st())
             if n_chunks:                                                      # sequences longer than one window
                 c = plan["chunks"]
-                _chk(lib.ruart_attn_train_bwd_long(hip.ptr(qkv), 3 * H, hip.ptr(d_ctx), H, hip.ptr(dqkv), 3 * H, H, self.nh, n_chunks,
-                                                   hip.ptr(c[0]), hip.ptr(c[1]), hip.ptr(c[2]), hip.ptr(c[3]), hip.ptr(c[4]), float(self.p_a),
-                                                   self._seed(l, 0), hip.ptr(lse), hip.ptr(self.delta_ws), hip.ptr(self.scale_ws),
-                                                   hip.ptr(self.bias_part_long), st()), "ruart_attn_train_bwd_long")
-                _chk(lib.ruart_colsum_f32_rows(hip.ptr(self.bias_part_long), n_chunks, 2 * H, 2 * H, hip.ptr(db), 1 if n_win else 0, st()),
-                     "ruart_colsum_f32_rows")
+                lib.ruart_attn_train_bwd_long(qkv, 3 * H, d_ctx, H, dqkv, 3 * H, H, self.nh, n_chunks, c[0], c[1], c[2], c[3], c[4],
+                                              float(self.p_a), self._seed(l, 0), lse, self.delta_ws, self.scale_ws, self.bias_part_long,
+                                              st())
+                lib.ruart_colsum_f32_rows(self.bias_part_long, n_chunks, 2 * H, 2 * H, db, 1 if n_win else 0, st())
             # the key bias shifts every score of a query row by the same q . b_k, which the softmax ignores: its gradient is
             # sum_i q_i sum_j dS_ij with sum_j dS_ij = 0 - exactly zero (the reference's 1e-9 is its own rounding noise)
             grads[a + "query.bias"], grads[a + "key.bias"], grads[a + "value.bias"] = db[:H] * scale, torch.zeros_like(db[:H]), db[H:]

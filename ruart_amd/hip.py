@@ -4,10 +4,15 @@ The library is plain HIP (no torch types in any signature): tensors cross the bo
 ``tensor.data_ptr()`` plus explicit sizes, and launches go to ``torch.cuda.current_stream()``.
 There is NO fallback: if the shared object cannot be loaded or built, importing a product module
 that needs it raises.
+
+Two typed handles on the one shared object.  ``kernels()`` is what the product modules launch through: a pointer argument takes the
+tensor itself (None: NULL; ``TensorPtr``), the stream stays explicit (``stream_ptr(device)``: the call site decides), and an entry point
+whose hipError_t is non-zero raises ``HipError`` naming the function really called.  ``load()`` is the raw surface - the ``int`` code
+comes back; ``ptr`` / ``check`` by hand - of tests, tools, the benchmark and the few product sites that read the code as a value.
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_longlong, c_size_t, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_longlong, c_size_t, c_uint, c_ulonglong, c_void_p
 
 import torch
 
@@ -55,34 +60,51 @@ class BertBatchC(Structure):
                 ("n_last_rows", c_int), ("last_rows", c_void_p)]
 
 
-_P, _I, _F, _LL = c_void_p, c_int, c_float, c_longlong
+class TensorPtr(c_void_p):
+    """Pointer argument of an entry point: a tensor (its ``data_ptr()``), None (NULL), a ``c_void_p`` (``ptr`` / ``stream_ptr``: passed
+    through), an int (a raw stream handle), or a host buffer of ctypes (the profiling entry points)."""
+
+    @classmethod
+    def from_param(cls, v):
+        if isinstance(v, torch.Tensor):         # the hot case first.  A c_void_p, never the bare int: ctypes passes that as a 32-bit C int
+            return c_void_p(v.data_ptr())
+        if v is None:
+            return c_void_p()
+        if isinstance(v, c_void_p):
+            return v
+        if isinstance(v, int):
+            return c_void_p(v)
+        return super().from_param(v)            # ctypes arrays, pointers, byref(...): whatever a plain c_void_p argument takes
+
+
+_P, _I, _F, _LL, _SZ, _U = TensorPtr, c_int, c_float, c_longlong, c_size_t, c_uint
 _SIGNATURES = {
     "ruart_version": (c_char_p, []),
     "ruart_gemm_16_nt": (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
-    "ruart_gemm_16_tail_ws_bytes": (c_size_t, [_I, _I, _I, _I]),
-    "ruart_gemm_16_nt_ws": (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, c_size_t, _I, _P]),
+    "ruart_gemm_16_tail_ws_bytes": (_SZ, [_I, _I, _I, _I]),
+    "ruart_gemm_16_nt_ws": (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _SZ, _I, _P]),
     "ruart_gemm_16c_nt": (_I, [_P, _P, _I, _P, _P, _I, _P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P]),
     "ruart_gemm_16c_nt_sel": (_I, [_P, _P, _I, _P, _P, _I, _P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
-    "ruart_gemm_16c_tail_ws_bytes": (c_size_t, [_I, _I, _I, _I]),
-    "ruart_gemm_16c_nt_ws": (_I, [_P, _P, _I, _P, _P, _I, _P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P, c_size_t, _I, _P]),
+    "ruart_gemm_16c_tail_ws_bytes": (_SZ, [_I, _I, _I, _I]),
+    "ruart_gemm_16c_nt_ws": (_I, [_P, _P, _I, _P, _P, _I, _P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P, _SZ, _I, _P]),
     "ruart_f16c_shifts": (_I, [POINTER(c_int)]),
     "ruart_gemm_16c_set_dual": (_I, [_I]),
-    "ruart_bert_set_correction": (_I, [_I, _I, _I, _I, ctypes.c_ulonglong]),
+    "ruart_bert_set_correction": (_I, [_I, _I, _I, _I, c_ulonglong]),
     "ruart_rows_layernorm_split": (_I, [_P, _I, _P, _P, _F, _P, _P, _P, _I, _I, _I, _P]),
     "ruart_bert_embed_ln_split": (_I, [_P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _I, _I, _I, _P]),
     "ruart_bert_attention_split": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ruart_bert_attention_split_set_heads": (_I, [_I]),
     "ruart_gemm_16_nt_splitk": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
     "ruart_gemm_16_nt_gelu2": (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
-    "ruart_gemm_16_nt_gelu_bwd_ws_floats": (c_size_t, [_I, _I]),
+    "ruart_gemm_16_nt_gelu_bwd_ws_floats": (_SZ, [_I, _I]),
     "ruart_gemm_16_nt_gelu_bwd": (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _I, _P, _I, _I, _I, _P]),
-    "ruart_colsum_f32_ws_floats": (c_size_t, [_I, _I]),
+    "ruart_colsum_f32_ws_floats": (_SZ, [_I, _I]),
     "ruart_colsum_f32": (_I, [_P, _I, _I, _I, _P, _I, _P, _P]),
     "ruart_colsum_f32_rows": (_I, [_P, _I, _I, _I, _P, _I, _P]),
     "ruart_gemm_16_tn_splitk": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
-    "ruart_ln_train_fwd": (_I, [_P, _I, _P, _I, _P, _P, _F, _F, ctypes.c_uint, _I, _P, _P, _P, _I, _I, _I, _P]),
-    "ruart_ln_train_bwd_ws_floats": (c_size_t, [_I]),
-    "ruart_ln_train_bwd": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _F, ctypes.c_uint, _I, _P, _I, _P, _I, _P, _P, _P, _I, _P, _I, _I, _P]),
+    "ruart_ln_train_fwd": (_I, [_P, _I, _P, _I, _P, _P, _F, _F, _U, _I, _P, _P, _P, _I, _I, _I, _P]),
+    "ruart_ln_train_bwd_ws_floats": (_SZ, [_I]),
+    "ruart_ln_train_bwd": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _F, _U, _I, _P, _I, _P, _I, _P, _P, _P, _I, _P, _I, _I, _P]),
     "ruart_gelu_bwd_rows": (_I, [_P, _P, _I, _P, _P, _I, _I, _P]),
     "ruart_f16_to_bf16": (_I, [_P, _P, _LL, _P]),
     "ruart_weight_prep": (_I, [_P, _I, _F, _P, _I, _P, _I, _I, _I, _P]),
@@ -93,10 +115,10 @@ _SIGNATURES = {
     "ruart_mix_rows": (_I, [_P, _LL, _I, _I, _P, _P, _I, _I, _I, _P]),
     "ruart_mix_rows_bwd": (_I, [_P, _LL, _I, _I, _P, _I, _P, _P, _I, _I, _P]),
     "ruart_rows_ln_to_16": (_I, [_P, _LL, _I, _P, _LL, _P, _P, _P, _LL, _I, _I, _I, _I, _I, _P]),
-    "ruart_attn_train_fwd": (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _F, ctypes.c_uint, _P]),
-    "ruart_attn_train_bwd": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _F, ctypes.c_uint, _P, _P]),
-    "ruart_attn_train_fwd_long": (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _F, ctypes.c_uint, _P, _P]),
-    "ruart_attn_train_bwd_long": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _F, ctypes.c_uint, _P, _P, _P, _P, _P]),
+    "ruart_attn_train_fwd": (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _F, _U, _P]),
+    "ruart_attn_train_bwd": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _F, _U, _P, _P]),
+    "ruart_attn_train_fwd_long": (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _F, _U, _P, _P]),
+    "ruart_attn_train_bwd_long": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _F, _U, _P, _P, _P, _P, _P]),
     "ruart_gemm_f32_nt": (_I, [_P, _I, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
     "ruart_bert_embed_ln": (_I, [_P, _P, _P, _P, _P, _P, _P, _F, _P, _I, _I, _I, _I, _P]),
     "ruart_rows_layernorm": (_I, [_P, _I, _P, _P, _F, _P, _I, _I, _I, _I, _P]),
@@ -106,10 +128,10 @@ _SIGNATURES = {
     "ruart_bert_pool_mix_bwd": (_I, [_P, _LL, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _P]),
     "ruart_rows_gather": (_I, [_P, _I, _P, _LL, _P, _LL, _I, _P, _LL, _P, _LL, _I, _P, _LL, _P, _LL, _I, _P]),
     "ruart_cast_f32_to_16": (_I, [_P, _P, _I, _LL, _F, _P]),
-    "ruart_bert_workspace_bytes": (c_size_t, [POINTER(BertModelC), _I]),
-    "ruart_bert_forward": (_I, [POINTER(BertModelC), POINTER(BertBatchC), _P, _P, c_size_t, _P]),
-    "ruart_bert_workspace_bytes_folded": (c_size_t, [POINTER(BertModelC), _I]),
-    "ruart_bert_forward_folded": (_I, [POINTER(BertModelC), POINTER(BertBatchC), _P, _P, _P, c_size_t, _P]),
+    "ruart_bert_workspace_bytes": (_SZ, [POINTER(BertModelC), _I]),
+    "ruart_bert_forward": (_I, [POINTER(BertModelC), POINTER(BertBatchC), _P, _P, _SZ, _P]),
+    "ruart_bert_workspace_bytes_folded": (_SZ, [POINTER(BertModelC), _I]),
+    "ruart_bert_forward_folded": (_I, [POINTER(BertModelC), POINTER(BertBatchC), _P, _P, _P, _SZ, _P]),
     "ruart_gemm_16c_nt_fold": (_I, [_P, _P, _I, _P, _P, _I, _P, _I, _P, _I, _P, _F, _P, _I, _P, _I, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
     "ruart_gemm_16_nt_fold": (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _P, _F, _P, _I, _P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _F, _I, _P]),
     "ruart_rows_stats_finish": (_I, [_P, _I, _I, _F, _F, _P, _P]),
@@ -143,31 +165,60 @@ _SIGNATURES = {
     "ruart_embedding_bwd_sorted": (_I, [_P, _P, _P, _P, _I, _I, _P, _P]),
     "ruart_embedding_bwd_split": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _P, _P, _P]),
     "ruart_phoc_table": (_I, [_P, _P, _I, _P, _I, _P, _P]),
-    "ruart_gemm_bf16_tn": (_I, [_P, ctypes.c_longlong, _P, ctypes.c_longlong, _P, _I, _I, _I, _I, _P, ctypes.c_size_t, _P]),
-    "ruart_gemm_x3_tn_grouped_ws": (c_size_t, [POINTER(X3TnProblemC), _I]),
-    "ruart_gemm_x3_tn_grouped": (_I, [POINTER(X3TnProblemC), _I, _P, c_size_t, _P]),
-    "ruart_gemm_x3_plan": (_I, [_I, _I, _I, _I, _I, POINTER(ctypes.c_int), POINTER(ctypes.c_size_t)]),
-    "ruart_gemm_x3": (_I, [_P, ctypes.c_longlong, ctypes.c_longlong, _P, ctypes.c_longlong, ctypes.c_longlong, _P, _P, _I, _I, _P, _I, _I,
-                           _I, _I, _P, ctypes.c_size_t, _P, _P, ctypes.c_float, _P, _I, _P]),
-    "ruart_gemm_x1": (_I, [_P, ctypes.c_longlong, ctypes.c_longlong, _P, ctypes.c_longlong, ctypes.c_longlong, _P, _P, _I, _I, _P, _I, _I,
-                           _I, _I, _P, ctypes.c_size_t, _P, _P, ctypes.c_float, _P, _I, _P]),
-    "ruart_stream_create_cu_masked": (_I, [_I, POINTER(ctypes.c_void_p)]),
-    "ruart_stream_create_priority": (_I, [_I, POINTER(ctypes.c_void_p)]),
+    "ruart_gemm_bf16_tn": (_I, [_P, _LL, _P, _LL, _P, _I, _I, _I, _I, _P, _SZ, _P]),
+    "ruart_gemm_x3_tn_grouped_ws": (_SZ, [POINTER(X3TnProblemC), _I]),
+    "ruart_gemm_x3_tn_grouped": (_I, [POINTER(X3TnProblemC), _I, _P, _SZ, _P]),
+    "ruart_gemm_x3_plan": (_I, [_I, _I, _I, _I, _I, POINTER(c_int), POINTER(_SZ)]),
+    "ruart_gemm_x3": (_I, [_P, _LL, _LL, _P, _LL, _LL, _P, _P, _I, _I, _P, _I, _I,
+                           _I, _I, _P, _SZ, _P, _P, _F, _P, _I, _P]),
+    "ruart_gemm_x1": (_I, [_P, _LL, _LL, _P, _LL, _LL, _P, _P, _I, _I, _P, _I, _I,
+                           _I, _I, _P, _SZ, _P, _P, _F, _P, _I, _P]),
+    "ruart_stream_create_cu_masked": (_I, [_I, POINTER(c_void_p)]),
+    "ruart_stream_create_priority": (_I, [_I, POINTER(c_void_p)]),
     "ruart_stream_destroy": (_I, [_P]),
     "ruart_gemm_set_tile_order": (_I, [_I]),
     "ruart_gemm_set_variant": (_I, [_I]),
     "ruart_prof_enable": (_I, [_I]),
-    "ruart_prof_read": (_I, [POINTER(ctypes.c_double), POINTER(c_longlong), POINTER(ctypes.c_double)]),
+    "ruart_prof_read": (_I, [POINTER(c_double), POINTER(_LL), POINTER(c_double)]),
     "ruart_prof_mark": (_I, [_I, _P]),
     "ruart_prof_timeline": (_I, [_P, _P, _P, _I, _P]),
 }
 
-_lib = None
+# entry points whose result is a value, not a hipError_t: no errcheck on the checked handle.  Every non-int restype (sizes, the version
+# string), and the ints that are a count (whole_ln_blocks), a granted priority level (negative on error: priority_stream reads it) or
+# the switch's previous state (set_dual).
+_UNCHECKED = frozenset({
+    "ruart_version", "ruart_gemm_16_tail_ws_bytes", "ruart_gemm_16c_tail_ws_bytes", "ruart_gemm_16_nt_gelu_bwd_ws_floats",
+    "ruart_colsum_f32_ws_floats", "ruart_ln_train_bwd_ws_floats", "ruart_bert_workspace_bytes", "ruart_bert_workspace_bytes_folded",
+    "ruart_gemm_x3_tn_grouped_ws", "ruart_whole_ln_blocks", "ruart_stream_create_priority", "ruart_gemm_16c_set_dual"})
+
+_lib = _checked = None
+
+
+class HipError(RuntimeError):
+    pass
+
+
+def _errcheck(rc, fn, args):
+    if rc != 0:
+        raise HipError("%s failed with hipError_t %d" % (fn.__name__, rc))
+    return rc
+
+
+def _typed(path, checked):
+    lib = ctypes.CDLL(path)
+    for name, (res, args) in _SIGNATURES.items():
+        fn = getattr(lib, name)          # AttributeError here = header/library mismatch: fail loudly
+        fn.restype = res
+        fn.argtypes = args
+        if checked and name not in _UNCHECKED:
+            fn.errcheck = _errcheck
+    return lib
 
 
 def load(build_if_missing=True):
-    """Load (building first if the .so is absent) and type every entry point."""
-    global _lib
+    """Load (building first if the .so is absent) and type every entry point; the raw handle (return codes as ints)."""
+    global _lib, _checked
     if _lib is not None:
         return _lib
     if not os.path.exists(LIB_PATH):
@@ -176,25 +227,25 @@ def load(build_if_missing=True):
         from . import build as _build
         _build.build(verbose=False)
     # RUART_HIP_LIB: load an experimental build of the same ABI instead (kernel A/B runs)
-    lib = ctypes.CDLL(os.environ.get("RUART_HIP_LIB") or LIB_PATH)
-    for name, (res, args) in _SIGNATURES.items():
-        fn = getattr(lib, name)          # AttributeError here = header/library mismatch: fail loudly
-        fn.restype = res
-        fn.argtypes = args
+    path = os.environ.get("RUART_HIP_LIB") or LIB_PATH
+    lib, checked = _typed(path, False), _typed(path, True)      # dlopen maps the object once: two sets of function objects, one set of switches
     if os.environ.get("RUART_GEMM_VARIANT"):             # experiments only: tile variant of the encoder GEMM (default 5)
         lib.ruart_gemm_set_variant(int(os.environ["RUART_GEMM_VARIANT"]))
     if os.environ.get("RUART_CORR_DUAL"):                # experiments only: the 256 x 128 two-workgroups-per-CU form of the fp16c QKV / intermediate
         lib.ruart_gemm_16c_set_dual(int(os.environ["RUART_CORR_DUAL"]))        # products (measured 5-8 % slower than the 256 x 256 form)
-    _lib = lib
+    _lib, _checked = lib, checked
     return lib
+
+
+def kernels():
+    """The checked handle (see the module docstring): tensors as pointer arguments, a non-zero return code raises HipError."""
+    if _checked is None:
+        load()
+    return _checked
 
 
 def exported_symbols():
     return sorted(_SIGNATURES)
-
-
-class HipError(RuntimeError):
-    pass
 
 
 def check(rc, what):
@@ -243,7 +294,7 @@ def ptr(t):
 def f16c_shifts():
     """(SA_LO, SA_HI, SW_HI, SW_LO): the exponents of the fp16c mode's e4m3 companions as compiled into the library (csrc/common.h)."""
     out = (c_int * 4)()
-    check(load().ruart_f16c_shifts(out), "ruart_f16c_shifts")
+    kernels().ruart_f16c_shifts(out)
     return tuple(int(v) for v in out)
 
 
@@ -259,11 +310,9 @@ def require_gpu(t, dtype=None):
 
 def cu_masked_stream(n_cus, device):
     """torch view of a HIP stream limited to ``n_cus`` compute units (ruart_stream_create_cu_masked)."""
-    import torch
-    lib = load()
-    out = ctypes.c_void_p()
+    out = c_void_p()
     with torch.cuda.device(device):
-        check(lib.ruart_stream_create_cu_masked(int(n_cus), ctypes.byref(out)), "ruart_stream_create_cu_masked")
+        kernels().ruart_stream_create_cu_masked(int(n_cus), ctypes.byref(out))
     # No atexit destroy: at interpreter exit the HIP runtime, RCCL and - under rocprofv3 - the profiler's tool library are torn
     # down in an order this module does not control; destroying the stream from an atexit hook after the profiler had finalised
     # is what ended a round-1 profiling run with SIGSEGV in __cxa_finalize (gpurun_out/pftrace.log: the masked stream was the
@@ -277,11 +326,9 @@ def cu_masked_stream(n_cus, device):
 def priority_stream(priority, device):
     """torch view of a non-blocking HIP stream of HIP priority ``priority`` (-1 high, 0 normal, 1 LOW - a level torch's stream pool
     does not offer; ruart_stream_create_priority)."""
-    import torch
-    lib = load()
-    out = ctypes.c_void_p()
+    out = c_void_p()
     with torch.cuda.device(device):
-        rc = lib.ruart_stream_create_priority(int(priority), ctypes.byref(out))
+        rc = load().ruart_stream_create_priority(int(priority), ctypes.byref(out))       # raw: the code is the level granted
     if rc < 0:
         raise HipError("ruart_stream_create_priority failed (%d)" % rc)
     st = torch.cuda.ExternalStream(out.value, device=device)
@@ -299,5 +346,5 @@ def destroy_stream(st):
     if handle is None:
         return
     st.synchronize()
-    load().ruart_stream_destroy(handle)
+    load().ruart_stream_destroy(handle)          # raw: a failed destroy (the runtime already torn down) is not an error here
     st._ruart_handle = None

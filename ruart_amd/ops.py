@@ -51,7 +51,7 @@ class _NanFlag:
     def ensure(self, device):
         if self.flag is None or self.flag.device != device:
             self.flag = torch.zeros(1, dtype=torch.int32, device=device)
-            hip.check(hip.load().ruart_set_nan_flag(hip.ptr(self.flag)), "ruart_set_nan_flag")
+            hip.kernels().ruart_set_nan_flag(self.flag)
         return self.flag
 
     def check_and_clear(self):
@@ -71,7 +71,7 @@ class _FusedAttention(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pa, pk, v, mask, diag, relu, pscale=None):
-        lib = hip.load()
+        lib = hip.kernels()
         for t in (pa, pk, v):
             hip.require_gpu(t, torch.float32)
         nan_flag.ensure(pa.device)
@@ -83,16 +83,15 @@ class _FusedAttention(torch.autograd.Function):
         if "attn" in _ABL_SKIP:
             out.zero_()
             probs.zero_()
-        rc = 0 if "attn" in _ABL_SKIP else lib.ruart_attn_fwd_pscale(hip.ptr(pa), hip.ptr(pk), hip.ptr(v), hip.ptr(mask), hip.ptr(diag), dl, int(relu),
-                                       hip.ptr(pscale), hip.ptr(out), hip.ptr(probs), B, L1, L2, h, D3, hip.stream_ptr())
-        hip.check(rc, "ruart_attn_fwd")
+        else:
+            lib.ruart_attn_fwd_pscale(pa, pk, v, mask, diag, dl, int(relu), pscale, out, probs, B, L1, L2, h, D3, hip.stream_ptr())
         ctx.save_for_backward(pa, pk, v, probs, diag, pscale)
         ctx.relu = int(relu)
         return out
 
     @staticmethod
     def backward(ctx, gout):
-        lib = hip.load()
+        lib = hip.kernels()
         pa, pk, v, probs, diag, pscale = ctx.saved_tensors
         B, L1, h = pa.shape
         L2, D3 = pk.shape[1], v.shape[2]
@@ -106,10 +105,9 @@ class _FusedAttention(torch.autograd.Function):
             for t in (ga, gk, gv, gdiag):
                 if t is not None:
                     t.zero_()
-        rc = 0 if "attn" in _ABL_SKIP else lib.ruart_attn_bwd_pscale(hip.ptr(pa), hip.ptr(pk), hip.ptr(v), hip.ptr(probs), hip.ptr(gout), hip.ptr(diag), dl, ctx.relu,
-                                       hip.ptr(pscale), hip.ptr(ga), hip.ptr(gk), hip.ptr(gv), hip.ptr(gdiag), hip.ptr(ds), B, L1, L2,
-                                       h, D3, hip.stream_ptr())
-        hip.check(rc, "ruart_attn_bwd")
+        else:
+            lib.ruart_attn_bwd_pscale(pa, pk, v, probs, gout, diag, dl, ctx.relu, pscale, ga, gk, gv, gdiag, ds, B, L1, L2, h, D3,
+                                      hip.stream_ptr())
         return ga, gk, gv, None, (colsum(gdiag).view_as(diag) if gdiag is not None else None), None, None
 
 
@@ -130,31 +128,28 @@ class _FusedScorer(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, u1, u2, uh, w, b, mask, ES, mask_flag):
-        lib = hip.load()
+        lib = hip.kernels()
         for t in (x, u1, u2, uh, w, b):
             hip.require_gpu(t, torch.float32)
         nan_flag.ensure(x.device)
         B, L, D = x.shape
         probs = torch.empty(B, L + 1, dtype=torch.float32, device=x.device)
         a = torch.empty(B, L, dtype=torch.float32, device=x.device)
-        hip.check(lib.ruart_scorer_fwd(hip.ptr(x), hip.ptr(u1), hip.ptr(u2), hip.ptr(uh), hip.ptr(w), hip.ptr(b), hip.ptr(mask), hip.ptr(probs),
-                                       hip.ptr(a), B, L, D, int(ES), int(bool(mask_flag)), hip.stream_ptr()), "ruart_scorer_fwd")
+        lib.ruart_scorer_fwd(x, u1, u2, uh, w, b, mask, probs, a, B, L, D, int(ES), int(bool(mask_flag)), hip.stream_ptr())
         ctx.save_for_backward(x, u1, u2, uh, w, probs, a)
         ctx.ES = int(ES)
         return probs
 
     @staticmethod
     def backward(ctx, gp):
-        lib = hip.load()
+        lib = hip.kernels()
         x, u1, u2, uh, w, probs, a = ctx.saved_tensors
         B, L, D = x.shape
         gp = gp.contiguous()
         gx = torch.empty_like(x)
         gu1, gu2, guh, gwp = (torch.empty(B, D, dtype=torch.float32, device=x.device) for _ in range(4))
         gbp = torch.empty(B, dtype=torch.float32, device=x.device)
-        hip.check(lib.ruart_scorer_bwd(hip.ptr(x), hip.ptr(u1), hip.ptr(u2), hip.ptr(uh), hip.ptr(w), hip.ptr(probs), hip.ptr(a), hip.ptr(gp),
-                                       hip.ptr(gx), hip.ptr(gu1), hip.ptr(gu2), hip.ptr(guh), hip.ptr(gwp), hip.ptr(gbp), B, L, D, ctx.ES,
-                                       hip.stream_ptr()), "ruart_scorer_bwd")
+        lib.ruart_scorer_bwd(x, u1, u2, uh, w, probs, a, gp, gx, gu1, gu2, guh, gwp, gbp, B, L, D, ctx.ES, hip.stream_ptr())
         return gx, gu1, gu2, guh, colsum(gwp).view_as(w), gbp.sum().view(1), None, None, None
 
 
@@ -170,26 +165,24 @@ class _WholeLayerNorm(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, eps):
-        lib = hip.load()
+        lib = hip.kernels()
         hip.require_gpu(x, torch.float32)
         nan_flag.ensure(x.device)
         y = torch.empty_like(x)
         stats = torch.empty(2, dtype=torch.float32, device=x.device)
         ws = _scratch(x.device, 2048)
-        hip.check(lib.ruart_whole_ln_fwd(hip.ptr(x), hip.ptr(y), hip.ptr(stats), hip.ptr(ws), x.numel(), eps, hip.stream_ptr()),
-                  "ruart_whole_ln_fwd")
+        lib.ruart_whole_ln_fwd(x, y, stats, ws, x.numel(), eps, hip.stream_ptr())
         ctx.save_for_backward(y, stats)
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        lib = hip.load()
+        lib = hip.kernels()
         y, stats = ctx.saved_tensors
         gy = gy.contiguous()
         gx = torch.empty_like(y)
         ws = _scratch(y.device, 2048)
-        hip.check(lib.ruart_whole_ln_bwd(hip.ptr(y), hip.ptr(gy), hip.ptr(stats), hip.ptr(gx), hip.ptr(ws), y.numel(),
-                                         hip.stream_ptr()), "ruart_whole_ln_bwd")
+        lib.ruart_whole_ln_bwd(y, gy, stats, gx, ws, y.numel(), hip.stream_ptr())
         return gx, None
 
 
@@ -209,31 +202,26 @@ def whole_ln_global_fwd(x, eps, group):
     """Forward of the cross-rank whole-tensor layer norm: (y, stats) with stats = (mean, rstd) of the tensors of all ranks of
     ``group`` taken together.  Two exchanges of P = ruart_whole_ln_blocks() floats per rank.  Every rank's ``x`` has the same
     number of elements (VQA_Sampler deals W equal shards), so the global count is W * x.numel(), exact."""
-    lib = hip.load()
+    lib = hip.kernels()
     hip.require_gpu(x, torch.float32)
     nan_flag.ensure(x.device)
     P, n, st = lib.ruart_whole_ln_blocks(), x.numel(), hip.stream_ptr()
-    part, world = _exchange_partials(group, P, lambda s: hip.check(lib.ruart_whole_ln_partials(
-        hip.ptr(x), None, hip.ptr(s), n, st), "ruart_whole_ln_partials"), x.device)
-    part2, _ = _exchange_partials(group, P, lambda s: hip.check(lib.ruart_whole_ln_var_global(
-        hip.ptr(x), n, hip.ptr(part), world, world * n, hip.ptr(s), st), "ruart_whole_ln_var_global"), x.device)
+    part, world = _exchange_partials(group, P, lambda s: lib.ruart_whole_ln_partials(x, None, s, n, st), x.device)
+    part2, _ = _exchange_partials(group, P, lambda s: lib.ruart_whole_ln_var_global(x, n, part, world, world * n, s, st), x.device)
     y = torch.empty_like(x)
     stats = torch.empty(2, dtype=torch.float32, device=x.device)
-    hip.check(lib.ruart_whole_ln_apply_global(hip.ptr(x), hip.ptr(y), n, eps, hip.ptr(part), hip.ptr(part2), world, world * n,
-                                              hip.ptr(stats), st), "ruart_whole_ln_apply_global")
+    lib.ruart_whole_ln_apply_global(x, y, n, eps, part, part2, world, world * n, stats, st)
     return y, stats
 
 
 def whole_ln_global_bwd(y, gy, stats, group):
     """grad_x of the cross-rank whole-tensor layer norm: one exchange of 2 P floats per rank (sum gy, sum gy * y)."""
-    lib = hip.load()
+    lib = hip.kernels()
     gy = gy.contiguous()
     P, n, st = lib.ruart_whole_ln_blocks(), y.numel(), hip.stream_ptr()
-    part, world = _exchange_partials(group, 2 * P, lambda s: hip.check(lib.ruart_whole_ln_partials(
-        hip.ptr(gy), hip.ptr(y), hip.ptr(s), n, st), "ruart_whole_ln_partials"), y.device)
+    part, world = _exchange_partials(group, 2 * P, lambda s: lib.ruart_whole_ln_partials(gy, y, s, n, st), y.device)
     gx = torch.empty_like(y)
-    hip.check(lib.ruart_whole_ln_bwd_global(hip.ptr(y), hip.ptr(gy), hip.ptr(stats), hip.ptr(gx), n, hip.ptr(part), world, world * n, st),
-              "ruart_whole_ln_bwd_global")
+    lib.ruart_whole_ln_bwd_global(y, gy, stats, gx, n, part, world, world * n, st)
     return gx
 
 
@@ -347,7 +335,7 @@ def mm(a, b, bias=None, mode=None, out=None, a_keep=None, b_keep=None, keep_scal
         if residual is not None:
             r = r + residual
         return r if out is None else out.copy_(r)
-    lib = hip.load()
+    lib = hip.kernels()
     if out is None:
         out = torch.empty(M, N, dtype=torch.float32, device=a.device)
     elif not (out.is_contiguous() and out.shape == (M, N) and out.dtype == torch.float32):
@@ -363,7 +351,7 @@ def mm(a, b, bias=None, mode=None, out=None, a_keep=None, b_keep=None, keep_scal
     ws_bytes = _PLAN_BYTES.get(pkey)
     if ws_bytes is None:                                   # (the plan is a pure function of the shape and the two layouts: asked once)
         nbytes = ctypes.c_size_t(0)
-        hip.check(lib.ruart_gemm_x3_plan(M, N, K, int(sak == 1), int(sbk == 1), None, ctypes.byref(nbytes)), "ruart_gemm_x3_plan")
+        lib.ruart_gemm_x3_plan(M, N, K, int(sak == 1), int(sbk == 1), None, ctypes.byref(nbytes))
         ws_bytes = _PLAN_BYTES[pkey] = int(nbytes.value)
     ws = _scratch(a.device, ws_bytes // 4, "x3") if ws_bytes else None
     fn = lib.ruart_gemm_x1 if mode == "x1" else lib.ruart_gemm_x3
@@ -374,9 +362,8 @@ def mm(a, b, bias=None, mode=None, out=None, a_keep=None, b_keep=None, keep_scal
         ldr = residual.stride(0)
     if "x3" in _ABL_SKIP:
         return out.zero_()
-    hip.check(fn(hip.ptr(a), sam, sak, hip.ptr(b), sbk, sbn, hip.ptr(bias), hip.ptr(residual), ldr, hip.ACT_NONE, hip.ptr(out), N,
-                 M, N, K, hip.ptr(ws), ws_bytes, hip.ptr(a_keep), hip.ptr(b_keep), float(keep_scale), hip.ptr(c_scale), int(rpm),
-                 hip.stream_ptr()), "ruart_gemm_x3")
+    fn(a, sam, sak, b, sbk, sbn, bias, residual, ldr, hip.ACT_NONE, out, N, M, N, K, ws, ws_bytes, a_keep, b_keep, float(keep_scale),
+       c_scale, int(rpm), hip.stream_ptr())
     return out
 
 
@@ -386,10 +373,10 @@ def colsum(x):
     if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1 and x.shape[0] > 64):
         return x.sum(0)
     rows, cols = x.shape
-    lib = hip.load()
+    lib = hip.kernels()
     out = torch.empty(cols, dtype=torch.float32, device=x.device)
     ws = _scratch(x.device, int(lib.ruart_colsum_f32_ws_floats(rows, cols)), "colsum")
-    hip.check(lib.ruart_colsum_f32(hip.ptr(x), x.stride(0), rows, cols, hip.ptr(out), 0, hip.ptr(ws), hip.stream_ptr(x.device)), "ruart_colsum_f32")
+    lib.ruart_colsum_f32(x, x.stride(0), rows, cols, out, 0, ws, hip.stream_ptr(x.device))
     return out
 
 
@@ -409,7 +396,7 @@ def _flush_weight_grads():
     items, _deferred = _deferred, []
     if not items:
         return
-    lib = hip.load()
+    lib = hip.kernels()
     dev = items[0][0].device
     with torch.cuda.device(dev):
         # the operands were produced on the trunk's three streams: this (the caller's) stream waits for each of them once, and the
@@ -444,7 +431,7 @@ def _flush_weight_grads():
                 q.accumulate = 1 if k > 0 else 0
             nbytes = int(lib.ruart_gemm_x3_tn_grouped_ws(arr, len(wave)))
             ws = _scratch(dev, nbytes // 4, "x3g") if nbytes else None
-            hip.check(lib.ruart_gemm_x3_tn_grouped(arr, len(wave), hip.ptr(ws), nbytes, hip.stream_ptr(dev)), "ruart_gemm_x3_tn_grouped")
+            lib.ruart_gemm_x3_tn_grouped(arr, len(wave), ws, nbytes, hip.stream_ptr(dev))
         for w, g in out.values():
             if w.grad is None:
                 w.grad = g
@@ -598,12 +585,11 @@ def _padded16(x, dtype, mult=256):
 
 def _gemm16(a16, w16, bias, M_out, dt):
     """a16 (Mp, K) . w16 (N, K)^T (+ bias) -> fp32 (M_out, N) on ruart_gemm_16_nt (the encoder's 256x256 MFMA kernel)."""
-    lib = hip.load()
+    lib = hip.kernels()
     Mp, K = a16.shape
     N = w16.shape[0]
     out = torch.empty(Mp, N, dtype=torch.float32, device=a16.device)
-    hip.check(lib.ruart_gemm_16_nt(hip.ptr(a16), K, hip.ptr(w16), K, hip.ptr(bias), None, 0, dt, hip.ptr(out), N, hip.DT_F32, Mp, N, K,
-                                   hip.ACT_NONE, dt, hip.stream_ptr()), "ruart_gemm_16_nt")
+    lib.ruart_gemm_16_nt(a16, K, w16, K, bias, None, 0, dt, out, N, hip.DT_F32, Mp, N, K, hip.ACT_NONE, dt, hip.stream_ptr())
     return out[:M_out]
 
 
@@ -635,16 +621,16 @@ class _Linear16(torch.autograd.Function):
 def _dw_bf16(gy, x):
     """dW (N, K) = gy^T . x for gy (rows, N), x (rows, K) fp32: one bf16 MFMA product with fp32 accumulation
     (ruart_gemm_bf16_tn), or the split-bf16 kernel when the operands are not laid out for it."""
-    lib = hip.load()
     rows, N = gy.shape
     K = x.shape[1]
     if not (gy.is_contiguous() and x.is_contiguous() and N % 4 == 0 and K % 4 == 0 and gy.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0):
         return mm(gy.t(), x, mode="x3")
     nbytes = ctypes.c_size_t(0)
-    hip.check(lib.ruart_gemm_x3_plan(N, K, rows, 0, 0, None, ctypes.byref(nbytes)), "ruart_gemm_x3_plan")
+    hip.kernels().ruart_gemm_x3_plan(N, K, rows, 0, 0, None, ctypes.byref(nbytes))
     ws = _scratch(gy.device, nbytes.value // 4, "x3") if nbytes.value else None
     out = torch.empty(N, K, dtype=torch.float32, device=gy.device)
-    rc = lib.ruart_gemm_bf16_tn(hip.ptr(gy), N, hip.ptr(x), K, hip.ptr(out), K, N, K, rows, hip.ptr(ws), nbytes.value, hip.stream_ptr())
+    # the raw handle: a non-zero code here means "not a shape of this kernel" and selects the split-bf16 product, it is not an error
+    rc = hip.load().ruart_gemm_bf16_tn(gy, N, x, K, out, K, N, K, rows, ws, nbytes.value, hip.stream_ptr())
     if rc != 0:
         return mm(gy.t(), x, mode="x3")
     return out
@@ -665,7 +651,7 @@ class _LstmRecurrence(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xproj, w_hh, ndir):
-        lib = hip.load()
+        lib = hip.kernels()
         hip.require_gpu(xproj, torch.float32)
         hip.require_gpu(w_hh, torch.float32)
         nan_flag.ensure(xproj.device)
@@ -682,8 +668,7 @@ class _LstmRecurrence(torch.autograd.Function):
                 if t is not None:
                     t.zero_()
         else:
-            hip.check(lib.ruart_lstm_fwd(hip.ptr(xproj), hip.ptr(w_hh), hip.ptr(y), hip.ptr(gates), hip.ptr(cells), hip.ptr(hprev), B, T, h,
-                                         ndir, hip.stream_ptr()), "ruart_lstm_fwd")
+            lib.ruart_lstm_fwd(xproj, w_hh, y, gates, cells, hprev, B, T, h, ndir, hip.stream_ptr())
         ctx.ndir, ctx.h = ndir, h
         ctx.mode = trunk_grad_gemm if trunk_gemm == "x3" else trunk_gemm
         ctx.save_for_backward(w_hh, gates, cells, hprev)
@@ -692,7 +677,7 @@ class _LstmRecurrence(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
-        lib = hip.load()
+        lib = hip.kernels()
         w_hh, gates, cells, hprev = ctx.saved_tensors
         ndir, h = ctx.ndir, ctx.h
         B, T, _ = ctx.shape
@@ -701,8 +686,7 @@ class _LstmRecurrence(torch.autograd.Function):
         if "lstm" in _ABL_SKIP:
             gx.zero_()
         else:
-            hip.check(lib.ruart_lstm_bwd(hip.ptr(gy), hip.ptr(w_hh), hip.ptr(gates), hip.ptr(cells), hip.ptr(gx), B, T, h, ndir,
-                                         hip.stream_ptr()), "ruart_lstm_bwd")
+            lib.ruart_lstm_bwd(gy, w_hh, gates, cells, gx, B, T, h, ndir, hip.stream_ptr())
         # grad_W_hh[d] = sum_{b,t} da[b,t,d] (x) h_prev[b,t,d]: one GEMM per direction on column slices (strided views, no copies)
         gw = None
         if ctx.needs_input_grad[1]:
@@ -732,9 +716,8 @@ class _LstmPackParams(torch.autograd.Function):
         w = torch.empty(2 * G, K, dtype=torch.float32, device=w_ih.device)
         b = torch.empty(2 * G, dtype=torch.float32, device=w_ih.device)
         whh = torch.empty(2, G, h, dtype=torch.float32, device=w_ih.device)
-        hip.check(hip.load().ruart_lstm_pack_params(hip.ptr(w_ih), hip.ptr(w_ih_r), hip.ptr(b_ih), hip.ptr(b_hh), hip.ptr(b_ih_r), hip.ptr(b_hh_r),
-                                                    hip.ptr(w_hh), hip.ptr(w_hh_r), hip.ptr(w), hip.ptr(b), hip.ptr(whh), G, K, h,
-                                                    hip.stream_ptr(w_ih.device)), "ruart_lstm_pack_params")
+        hip.kernels().ruart_lstm_pack_params(w_ih, w_ih_r, b_ih, b_hh, b_ih_r, b_hh_r, w_hh, w_hh_r, w, b, whh, G, K, h,
+                                             hip.stream_ptr(w_ih.device))
         ctx.G = G
         return w, b, whh
 
@@ -778,29 +761,27 @@ class _LstmCell(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pre, h_prev, c_prev, n_active):
-        lib = hip.load()
+        lib = hip.kernels()
         for t in (pre, h_prev, c_prev):
             hip.require_gpu(t, torch.float32)
         N, h = h_prev.shape
         h_out, c_out = torch.empty_like(h_prev), torch.empty_like(c_prev)
         acts = torch.empty_like(pre)
-        hip.check(lib.ruart_lstm_cell_fwd(hip.ptr(pre), hip.ptr(h_prev), hip.ptr(c_prev), hip.ptr(h_out), hip.ptr(c_out),
-                                          hip.ptr(acts), n_active, N, h, hip.stream_ptr()), "ruart_lstm_cell_fwd")
+        lib.ruart_lstm_cell_fwd(pre, h_prev, c_prev, h_out, c_out, acts, n_active, N, h, hip.stream_ptr())
         ctx.save_for_backward(acts, c_prev, c_out)
         ctx.n_active = n_active
         return h_out, c_out
 
     @staticmethod
     def backward(ctx, gh, gc):
-        lib = hip.load()
+        lib = hip.kernels()
         acts, c_prev, c_out = ctx.saved_tensors
         N, h = c_prev.shape
         gh = gh.contiguous() if gh is not None else None
         gc = gc.contiguous() if gc is not None else None
         g_pre = torch.empty_like(acts)
         g_h, g_c = torch.empty_like(c_prev), torch.empty_like(c_prev)
-        hip.check(lib.ruart_lstm_cell_bwd(hip.ptr(gh), hip.ptr(gc), hip.ptr(acts), hip.ptr(c_prev), hip.ptr(c_out), hip.ptr(g_pre),
-                                          hip.ptr(g_h), hip.ptr(g_c), ctx.n_active, N, h, hip.stream_ptr()), "ruart_lstm_cell_bwd")
+        lib.ruart_lstm_cell_bwd(gh, gc, acts, c_prev, c_out, g_pre, g_h, g_c, ctx.n_active, N, h, hip.stream_ptr())
         return g_pre, g_h, g_c, None
 
 
@@ -817,8 +798,8 @@ class _RowScale(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, mask, row_of):
         y = torch.empty_like(x)
-        hip.check(hip.load().ruart_rows_scale(hip.ptr(x), x.stride(0), hip.ptr(mask), mask.stride(0), hip.ptr(row_of), hip.ptr(y), y.stride(0),
-                                              x.shape[0], x.shape[1], hip.stream_ptr(x.device)), "ruart_rows_scale")
+        hip.kernels().ruart_rows_scale(x, x.stride(0), mask, mask.stride(0), row_of, y, y.stride(0), x.shape[0], x.shape[1],
+                                       hip.stream_ptr(x.device))
         ctx.save_for_backward(mask, row_of)
         return y
 
@@ -828,8 +809,8 @@ class _RowScale(torch.autograd.Function):
         if g.stride(1) != 1 or g.stride(0) % 4 or g.data_ptr() % 16:
             g = g.contiguous()
         gx = torch.empty(g.shape, dtype=torch.float32, device=g.device)
-        hip.check(hip.load().ruart_rows_scale(hip.ptr(g), g.stride(0), hip.ptr(mask), mask.stride(0), hip.ptr(row_of), hip.ptr(gx), gx.stride(0),
-                                              g.shape[0], g.shape[1], hip.stream_ptr(g.device)), "ruart_rows_scale")
+        hip.kernels().ruart_rows_scale(g, g.stride(0), mask, mask.stride(0), row_of, gx, gx.stride(0), g.shape[0], g.shape[1],
+                                       hip.stream_ptr(g.device))
         return gx, None, None
 
 
@@ -849,19 +830,18 @@ def embedding_grad(gy, sort, shape):
     their ids (batch._sort_ids): 3 tensors = one workgroup per looked-up row; 4 tensors = the two-level form for rows with very many
     occurrences.  Ordered sums, no atomics: the same bits every run."""
     V, D = shape
-    lib = hip.load()
+    lib = hip.kernels()
     gw = torch.zeros(V, D, dtype=torch.float32, device=gy.device)
     gy = gy.reshape(-1, D).contiguous()
     if len(sort) == 3:
         order, seg_start, seg_row = sort
-        hip.check(lib.ruart_embedding_bwd_sorted(hip.ptr(gy), hip.ptr(order), hip.ptr(seg_start), hip.ptr(seg_row), seg_row.numel(), D, hip.ptr(gw),
-                                                 hip.stream_ptr(gy.device)), "ruart_embedding_bwd_sorted")
+        lib.ruart_embedding_bwd_sorted(gy, order, seg_start, seg_row, seg_row.numel(), D, gw, hip.stream_ptr(gy.device))
     else:
         order, sub_start, row_first, row_id = sort
         n_sub = sub_start.numel() - 1
         ws = torch.empty(max(n_sub, 1), D, dtype=torch.float32, device=gy.device)
-        hip.check(lib.ruart_embedding_bwd_split(hip.ptr(gy), hip.ptr(order), hip.ptr(sub_start), n_sub, hip.ptr(row_first), hip.ptr(row_id),
-                                                row_id.numel(), D, hip.ptr(ws), hip.ptr(gw), hip.stream_ptr(gy.device)), "ruart_embedding_bwd_split")
+        lib.ruart_embedding_bwd_split(gy, order, sub_start, n_sub, row_first, row_id, row_id.numel(), D, ws, gw,
+                                      hip.stream_ptr(gy.device))
     return gw
 
 

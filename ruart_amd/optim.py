@@ -106,21 +106,18 @@ class FusedAdamax:
             clr[i] = g0["lr"] / (1.0 - g0["betas"][0] ** self.steps[id(p)])
         pl["gptr"].copy_(pl["gptr_host"][slot], non_blocking=True)
         clr_dev = pl["gptr"][n_live:].view(torch.float32)
-        lib = hip.load()
+        lib = hip.kernels()
         st = hip.stream_ptr()
         self.step_count += 1
         coef = None
         if max_norm is not None:
             ct, cs, cc, n = pl["norm"] if extra_sq is None else pl["upd"]
-            hip.check(lib.ruart_grad_norm_clip(hip.ptr(pl["gptr"]), hip.ptr(ct), hip.ptr(cs), hip.ptr(cc), n, float(max_norm),
-                                               hip.ptr(pl["partial"]), hip.ptr(self.norm_coef), hip.ptr(extra_sq), st),
-                      "ruart_grad_norm_clip")
+            lib.ruart_grad_norm_clip(pl["gptr"], ct, cs, cc, n, float(max_norm), pl["partial"], self.norm_coef, extra_sq, st)
             coef = self.norm_coef
         ct, cs, cc, n = pl["upd"]
         ptrs = pl["ptrs"]
-        hip.check(lib.ruart_adamax_step(hip.ptr(ptrs[0]), hip.ptr(pl["gptr"]), hip.ptr(ptrs[1]), hip.ptr(ptrs[2]), hip.ptr(ct), hip.ptr(cs),
-                                        hip.ptr(cc), n, hip.ptr(coef), hip.ptr(clr_dev), float(g0["betas"][0]), float(g0["betas"][1]),
-                                        float(g0["eps"]), st), "ruart_adamax_step")
+        lib.ruart_adamax_step(ptrs[0], pl["gptr"], ptrs[1], ptrs[2], ct, cs, cc, n, coef, clr_dev, float(g0["betas"][0]),
+                              float(g0["betas"][1]), float(g0["eps"]), st)
         # the kernel wrote the parameters through raw pointers: tell torch (version counters feed autograd's saved-tensor checks and
         # the trainable encoder's operand cache, bert_train16.accurate_weights)
         bump = getattr(torch.autograd.graph, "increment_version", None)

@@ -18,7 +18,7 @@ def normalize(token):
 
 def phoc_table(words, device="cuda", normalized=False):
     """Rows of 0/1 fp32, one per word, on ``device``."""
-    lib = hip.load()
+    lib = hip.kernels()
     device = torch.device(device)
     if device.type != "cuda":
         raise hip.HipError("phoc_table runs on the GPU (got device %s)" % device)
@@ -34,8 +34,7 @@ def phoc_table(words, device="cuda", normalized=False):
         d_chars = torch.from_numpy(chars.copy()).to(device)
         d_off = torch.from_numpy(offsets).to(device)
         status = torch.zeros(1, dtype=torch.int32, device=device)
-        rc = lib.ruart_phoc_table(hip.ptr(d_chars), hip.ptr(d_off), len(words), hip.ptr(out), PHOC_DIM, hip.ptr(status), hip.stream_ptr())
-        hip.check(rc, "ruart_phoc_table")
+        lib.ruart_phoc_table(d_chars, d_off, len(words), out, PHOC_DIM, status, hip.stream_ptr())
         bad = int(status.item())
     if bad:
         raise RuntimeError("Error: unigram outside [a-z0-9] in word %r" % words[bad - 1])
