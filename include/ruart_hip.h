@@ -514,12 +514,21 @@ int ruart_phoc_table(const unsigned char* chars, const int* offsets, int n_words
  *   ruart_adamax_step:    g' = g * norm_coef[1] (norm_coef NULL: no clipping);  m += (1 - beta1)(g' - m);  u = max(beta2 u, |g'| + eps);
  *                         p -= clr[t] * m / u  with clr[t] = lr / (1 - beta1^step_t), one DEVICE float per tensor (torch.optim.Adamax
  *                         counts the steps of every parameter separately).
+ *   ruart_adam_step:      the Adam-family group of a trained encoder, same addressing (its own tables and chunk list; tensor indices
+ *                         count inside the group).  g' = g * norm_coef[1] (NULL: no clipping);  m = beta1 m + (1 - beta1) g';
+ *                         v = beta2 v + (1 - beta2) g'^2;  p = p dec - a m / (sqrt(v) c + eps)  with {a, dec, c} = tab[3 t .. 3 t + 2], three
+ *                         DEVICE floats per tensor.  torch.optim.AdamW: a = lr_t / (1 - beta1^k), c = 1 / sqrt(1 - beta2^k), dec = 1 - lr_t wd
+ *                         (k: the tensor's own step count, this step included); BertAdam (Models/Bert/optimization.py:129-152, no bias
+ *                         correction): a = lr_t, c = 1, dec = 1 - lr_t wd.
  * The update's chunk list may leave out elements (embedding rows the trainer re-pins every step): they are not touched. */
 int ruart_grad_norm_clip(const float* const* grads, const int* c_tensor, const int* c_start, const int* c_count, int n_chunks,
                          float max_norm, float* partial, float* norm_coef, const float* extra_sq, void* stream);
 int ruart_adamax_step(float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_inf, const int* c_tensor,
                       const int* c_start, const int* c_count, int n_chunks, const float* norm_coef, const float* clr, float beta1,
                       float beta2, float eps, void* stream);
+int ruart_adam_step(float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq, const int* c_tensor,
+                    const int* c_start, const int* c_count, int n_chunks, const float* norm_coef, const float* tab, float beta1,
+                    float beta2, float eps, void* stream);
 
 /* NaN contract of the reference (assert torch.sum(torch.isnan(x)) == 0, Layers.py:169,290,430,462,467): after this
  * call every SDNet kernel ORs 1 into *flag (a device int) when it writes a NaN; the Python layer checks and clears it

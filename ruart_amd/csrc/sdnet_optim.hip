@@ -5,6 +5,8 @@
 // step (rows >= tune_partial, :369-373) are left out of the update (their gradients still count in the norm, as in the
 // reference).  Tensors are addressed through device tables of pointers; work is cut into chunks of 8192 elements
 // (tensor index, start, count), one workgroup per chunk.  All sums run in a fixed order: deterministic.
+// A trained encoder may step as a group of its own (opt['bert_optimizer']): one more launch, ruart_adam_step, over its chunks, under the
+// same device-resident clip coefficient (the norm runs once over the gradients of both groups).
 #include "common.h"
 #include "ruart_hip.h"
 
@@ -85,6 +87,49 @@ __global__ __launch_bounds__(256) void adamax_update_kernel(float* const* __rest
   }
 }
 
+// Adam family of the trained encoder's group (torch.optim.AdamW, and the reference's BertAdam, Models/Bert/optimization.py:129-152), one
+// form for both:  m = b1 m + (1 - b1) g';  v = b2 v + (1 - b2) g'^2;  p = p dec - a m / (sqrt(v) c + eps).  What differs between the rules,
+// the tensors (decay or none, own step count) and the steps (schedule) is the host's: tab[3 t] = {a, dec, c}.
+__global__ __launch_bounds__(256) void adam_update_kernel(float* const* __restrict__ params, const float* const* __restrict__ grads,
+                                                          float* const* __restrict__ exp_avg, float* const* __restrict__ exp_avg_sq,
+                                                          const int* __restrict__ c_tensor, const int* __restrict__ c_start,
+                                                          const int* __restrict__ c_count, const float* __restrict__ coef_ptr,
+                                                          const float* __restrict__ tab, float b1, float b2, float eps) {
+  const int c = blockIdx.x, t = c_tensor[c], s0 = c_start[c], n = c_count[c];
+  const float coef = coef_ptr ? coef_ptr[1] : 1.0f;
+  const float a = tab[3 * t], dec = tab[3 * t + 1], cs = tab[3 * t + 2];
+  const float one_minus_b1 = 1.0f - b1, one_minus_b2 = 1.0f - b2;
+  float* p = params[t] + s0;
+  const float* g = grads[t] + s0;
+  float* m = exp_avg[t] + s0;
+  float* v = exp_avg_sq[t] + s0;
+  for (int i = threadIdx.x * 4; i < n; i += 1024) {
+    if (i + 3 < n) {
+      f32x4_t pv = *reinterpret_cast<f32x4_t*>(p + i), mv = *reinterpret_cast<f32x4_t*>(m + i), vv = *reinterpret_cast<f32x4_t*>(v + i);
+      const f32x4_t gv = *reinterpret_cast<const f32x4_t*>(g + i);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float gr = gv[r] * coef;
+        mv[r] = b1 * mv[r] + one_minus_b1 * gr;
+        vv[r] = b2 * vv[r] + one_minus_b2 * gr * gr;
+        pv[r] = pv[r] * dec - a * (mv[r] / (sqrtf(vv[r]) * cs + eps));
+      }
+      *reinterpret_cast<f32x4_t*>(p + i) = pv;
+      *reinterpret_cast<f32x4_t*>(m + i) = mv;
+      *reinterpret_cast<f32x4_t*>(v + i) = vv;
+    } else {
+      for (int j = i; j < n; ++j) {
+        const float gr = g[j] * coef;
+        const float mj = b1 * m[j] + one_minus_b1 * gr;
+        const float vj = b2 * v[j] + one_minus_b2 * gr * gr;
+        m[j] = mj;
+        v[j] = vj;
+        p[j] = p[j] * dec - a * (mj / (sqrtf(vj) * cs + eps));
+      }
+    }
+  }
+}
+
 extern "C" int ruart_grad_norm_clip(const float* const* grads, const int* c_tensor, const int* c_start, const int* c_count, int n_chunks,
                                     float max_norm, float* partial, float* norm_coef, const float* extra_sq, void* stream) {
   RUART_ENTRY();
@@ -103,6 +148,17 @@ extern "C" int ruart_adamax_step(float* const* params, const float* const* grads
   if (n_chunks <= 0 || !clr || !params || !grads || !exp_avg || !exp_inf) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(adamax_update_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg, exp_inf, c_tensor,
                      c_start, c_count, norm_coef, clr, 1.0f - beta1, beta2, eps);
+  RUART_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int ruart_adam_step(float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                               const int* c_tensor, const int* c_start, const int* c_count, int n_chunks, const float* norm_coef,
+                               const float* tab, float beta1, float beta2, float eps, void* stream) {
+  RUART_ENTRY();
+  if (n_chunks <= 0 || !tab || !params || !grads || !exp_avg || !exp_avg_sq || !c_tensor || !c_start || !c_count) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(adam_update_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg, exp_avg_sq, c_tensor,
+                     c_start, c_count, norm_coef, tab, beta1, beta2, eps);
   RUART_CHECK_LAUNCH();
   return 0;
 }

@@ -214,6 +214,8 @@ class SDNetTrainer(BaseTrainer):
 
     # -- model / optimizer ------------------------------------------------------------------------------------
     def setup_model(self, vocab_embedding):
+        from .optim import check_bert_optimizer
+        bert_group = check_bert_optimizer(self.opt)          # opt['bert_optimizer']: refuses a conf that cannot have the group (ValueError)
         if self.opt.get("dp_global_batch"):
             if self.opt.get("dp_overlap_backward"):
                 raise ValueError("opt['dp_global_batch'] does not combine with opt['dp_overlap_backward']: the gradient hooks' collectives "
@@ -234,13 +236,21 @@ class SDNetTrainer(BaseTrainer):
         if o == "ADAM":
             self.optimizer = optim.Adamax(params, weight_decay=0.5, lr=1e-3)
         elif o == "#":
-            if self.device.type == "cuda" and self.opt.get("ruart_fused_optimizer", True):
+            fused = self.device.type == "cuda" and self.opt.get("ruart_fused_optimizer", True)
+            pinned = {}
+            if "TUNE_PARTIAL" in self.opt and (fused or bert_group is not None):
+                # rows >= tune_partial are re-pinned after every step: the fused optimizers never update them
+                for flag, name in (("FastText", "fast_embed"), ("GLOVE", "glove_embed")):
+                    if flag in self.opt and getattr(self.network, name).weight.requires_grad:
+                        pinned[getattr(self.network, name).weight] = self.opt["tune_partial"]
+            if bert_group is not None:
+                # opt['bert_optimizer']: the trained encoder steps as an Adam-family group of its own, the rest stays under Adamax
+                from .optim import AdamaxAdam, FusedAdamaxAdam, split_parameters
+                trunk, encoder, no_decay = split_parameters(self.network.named_parameters())
+                self.optimizer = (FusedAdamaxAdam if fused else AdamaxAdam)(trunk, encoder, no_decay, lr=self.opt.get("lr", 2e-3),
+                                                                            pinned=pinned, **bert_group)
+            elif fused:
                 from .optim import FusedAdamax
-                pinned = {}
-                if "TUNE_PARTIAL" in self.opt:          # rows >= tune_partial are re-pinned after every step: never updated
-                    for flag, name in (("FastText", "fast_embed"), ("GLOVE", "glove_embed")):
-                        if flag in self.opt and getattr(self.network, name).weight.requires_grad:
-                            pinned[getattr(self.network, name).weight] = self.opt["tune_partial"]
                 self.optimizer = FusedAdamax(params, lr=self.opt.get("lr", 2e-3), pinned=pinned)
             else:
                 self.optimizer = optim.Adamax(params, lr=self.opt.get("lr", 2e-3))

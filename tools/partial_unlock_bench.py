@@ -7,6 +7,9 @@ Bench workload (B = 64, 30-word questions, 100 OCR items, 36 objects, bert-base,
 
     python tools/partial_unlock_bench.py [--rounds 3] [--modes lock,full,n1,n2,n4,n6,n2-inline] [--child-timeout 240]
 
+(a mode ``n<N>-adamw``, not in the default list, steps the trained layers under opt['bert_optimizer'] = 'adamw'; the table's ratio
+columns need ``full`` / ``lock`` among the modes and show ``-`` otherwise)
+
 Every mode runs in a FRESH child process (a second CU-masked stream in one process lands on a used hardware queue slot), one after the
 other, each under its own time limit; the chain stops at the first child that fails.  The rounds alternate through the modes inside one
 invocation, and only ratios inside one invocation mean anything: boxes differ by 5 %.  Per mode: ms per step, samples / s, peak
@@ -43,6 +46,8 @@ def child(mode, steps, warmup):
         opt["bert_train_layers"] = int(mode[1:].split("-")[0])
         if mode.endswith("-inline"):
             opt["bert_train_prefetch"] = False
+        if mode.endswith("-adamw"):          # e.g. n2-adamw: the trained layers as an Adam group of their own (opt['bert_optimizer'])
+            opt["bert_optimizer"] = "adamw"
     tr, _ = bench.build_trainer(opt, synth.bert_config(), dev)
     bs = [tr.ToCUDA(synth.synthetic_batch(opt, BATCH, seed=7 + i, n_q=30, n_ocr=100, n_od=36)) for i in range(4)]
     tokens = bs[0][0]["_ruart_index"].packed.T
