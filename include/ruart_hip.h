@@ -441,6 +441,29 @@ int ruart_scorer_bwd(const float* x, const float* u1, const float* u2, const flo
                      const float* a_in, const float* gprobs, float* gx, float* gu1, float* gu2, float* guh, float* gw_part,
                      float* gb_part, int B, int L, int D, int ES, void* stream);
 
+/* The scorer with H pooled heads beside the slot scores (label_yesno: Layers.py:405-416, with or without useES / no_answer).
+ * uh (B, H, D), w (H, D), bh (H): per head h  a_h = softmax_i(mask(x_i . uh_h)),  s_h = w_h . sum_i a_hi x_i + bh_h  (masked slots
+ * never enter a pool; the slot scores x_i . u(i) - u2 for i < ES, u1 for the rest, ES = 0: no split - are masked only with mask_flag).
+ *   probs (B, H + L) = softmax([s_0 .. s_{n_front-1}, score_0 .. score_{L-1}, s_{n_front} .. s_{H-1}])
+ * i.e. the first n_front heads in front of the slots, the others behind them: H = 4, n_front = 3 with the heads ordered
+ * no_read, yes, no, noanswer is Layers.py:411 followed by :416.  a_out (B, H, L): the pooling weights, kept for the backward.
+ * One workgroup per sample, every sum in a fixed order (bit-equal from run to run); x is read twice by the forward and three times by
+ * the backward whatever H.  The NaN flag (ruart_set_nan_flag) is raised on a NaN probability.
+ * Contract: B >= 1, 1 <= H <= 4, 0 <= n_front <= H, 0 <= ES < L <= 1024, D % 4 == 0, no NULL pointer (ES = 0: u2 / gu2 are still
+ * read / written - pass any (B, D) buffers), and the kernels' LDS - all dynamic, none static - within the 64 KiB a kernel may use
+ * without opting in to more:
+ *   4 * (4 + up4(H + L) + 2 * H * up4(L) + H * D) <= 65536      up4(n) = n rounded up to a multiple of 4
+ * (11.6 KB at L = 100, D = 500, H = 4; both directions check the backward's size, so a forward that ran has a backward).  Anything
+ * else returns hipErrorInvalidValue and launches nothing. */
+int ruart_scorer_heads_fwd(const float* x, const float* u1, const float* u2, const float* uh, const float* w, const float* bh,
+                           const unsigned char* mask, float* probs, float* a_out, int B, int L, int D, int ES, int H, int n_front,
+                           int mask_flag, void* stream);
+/* gradients of the above for gprobs (B, H + L): gx (B, L, D), gu1 / gu2 (B, D), guh (B, H, D), and per-sample partials gw_part (B, H, D),
+ * gb_part (B, H) whose sums over the batch are d w, d bh.   gx_i = ds_i u(i) + sum_h (a_hi dpool_h + dz_hi uh_h). */
+int ruart_scorer_heads_bwd(const float* x, const float* u1, const float* u2, const float* uh, const float* w, const float* probs,
+                           const float* a_in, const float* gprobs, float* gx, float* gu1, float* gu2, float* guh, float* gw_part,
+                           float* gb_part, int B, int L, int D, int ES, int H, int n_front, void* stream);
+
 /* LSTM recurrence (what Layers.py:166 delegates to nn.LSTM), BOTH directions of one layer per call
  * (grid = B x ndir), gate order i,f,g,o, zero initial state, padding not masked.
  *   xproj : (B, T, ndir*4h)  x W_ih^T + b_ih + b_hh, direction d at column offset d*4h (one GEMM by the caller)

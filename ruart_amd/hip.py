@@ -152,6 +152,8 @@ _SIGNATURES = {
     "ruart_whole_ln_bwd_global": (_I, [_P, _P, _P, _P, _LL, _P, _I, _LL, _P]),
     "ruart_scorer_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "ruart_scorer_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "ruart_scorer_heads_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "ruart_scorer_heads_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "ruart_lstm_set_variant": (_I, [_I]),
     "ruart_lstm_pack_params": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "ruart_lstm_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
@@ -202,7 +204,9 @@ class HipError(RuntimeError):
 
 def _errcheck(rc, fn, args):
     if rc != 0:
-        raise HipError("%s failed with hipError_t %d" % (fn.__name__, rc))
+        err = HipError("%s failed with hipError_t %d" % (fn.__name__, rc))
+        err.code = rc                    # (a caller with a fallback for a refused shape tells hipErrorInvalidValue from a real failure)
+        raise err
     return rc
 
 

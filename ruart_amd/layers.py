@@ -286,28 +286,40 @@ class BilinearSeqAttn(nn.Module):
 
 
 class GetFinalScores(nn.Module):
-    """Layers.py:352-432 (useES / no_answer branches of the shipped conf).  ``rnn`` (GRUCell) is kept so the
-    checkpoint keys match; the reference computes one step of it and discards the result (:395-397) - it never
-    receives a gradient, and it is not computed here."""
+    """Layers.py:352-432.  ``rnn`` (GRUCell) is kept so the checkpoint keys match; the reference computes one step of it and
+    discards the result (:395-397) - it never receives a gradient, and it is not computed here.  ``yesno`` (conf key label_yesno)
+    adds the three pooled heads no_read / yes / no in front of the slot scores (:405-411)."""
 
     def __init__(self, x_size, h_size, yesno, no_answer, useES):
         super().__init__()
-        if yesno:
-            raise NotImplementedError("label_yesno is not in the shipped configuration")
         self.no_answer, self.yesno, self.useES = no_answer, yesno, useES
         if no_answer:
             self.noanswer_linear = nn.Linear(h_size, x_size)
             self.noanswer_w = nn.Linear(x_size, 1, bias=True)
+        if yesno:
+            self.no_linear = nn.Linear(h_size, x_size)
+            self.no_w = nn.Linear(x_size, 1, bias=True)
+            self.yes_linear = nn.Linear(h_size, x_size)
+            self.yes_w = nn.Linear(x_size, 1, bias=True)
+            self.no_read_linear = nn.Linear(h_size, x_size)
+            self.no_read_w = nn.Linear(x_size, 1, bias=True)
         self.attn = BilinearSeqAttn(x_size, h_size)
         self.rnn = nn.GRUCell(x_size, h_size)
         self.attn2 = BilinearSeqAttn(x_size, h_size)
 
     def forward(self, x, h0, x_mask, ES_len, mask_flag=None):
-        if (self.useES and self.no_answer and x.is_cuda and ops.trunk_gemm == "x3" and x.dim() == 3 and x.size(2) % 4 == 0
-                and x.size(1) <= 1024 and 0 < ES_len < x.size(1) and fused_scorer_enabled
-                # the fused form models the dropout of x only as the variational (B, D) mask; without VARIATIONAL_DROPOUT the
-                # reference drops x element-wise (Layers.py:32-39, 454): those configurations take the op-by-op form below
-                and (do_seq_dropout or not self.training or dropout_p == 0)):
+        fusable = (x.is_cuda and ops.trunk_gemm == "x3" and x.dim() == 3 and x.size(2) % 4 == 0 and x.size(1) <= 1024
+                   and fused_scorer_enabled
+                   # the fused forms model the dropout of x only as the variational (B, D) mask; without VARIATIONAL_DROPOUT the
+                   # reference drops x element-wise (Layers.py:32-39, 454): those configurations take the op-by-op form below
+                   and (do_seq_dropout or not self.training or dropout_p == 0))
+        if fusable and self.yesno and (not self.useES or 0 < ES_len < x.size(1)):
+            try:
+                return self._forward_fused_heads(x, h0, x_mask, ES_len if self.useES else 0, mask_flag)
+            except ops.hip.HipError as e:
+                if getattr(e, "code", None) != 1:       # hipErrorInvalidValue: a shape outside the entry point's contract (its LDS rule)
+                    raise
+        elif fusable and not self.yesno and self.useES and self.no_answer and 0 < ES_len < x.size(1):
             return self._forward_fused(x, h0, x_mask, ES_len, mask_flag)
         if self.useES:
             score_ocr = self.attn(x[:, ES_len:], h0, x_mask[:, ES_len:], mask_flag=mask_flag)
@@ -315,28 +327,60 @@ class GetFinalScores(nn.Module):
             score_s = torch.cat([score_es, score_ocr], dim=-1)
         else:
             score_s = self.attn(x, h0, x_mask, mask_flag=mask_flag)
+        if self.yesno:
+            # (sic) h0 is overwritten: the no-answer head below drops the already dropped vector again (:406, :414).  h0 is 2-D:
+            # element-wise dropout whatever VARIATIONAL_DROPOUT says
+            h0 = dropout(h0, p=dropout_p, training=self.training)
+            score_no = self.get_single_score(x, h0, x_mask, self.no_linear, self.no_w)
+            score_yes = self.get_single_score(x, h0, x_mask, self.yes_linear, self.yes_w)
+            score_noread = self.get_single_score(x, h0, x_mask, self.no_read_linear, self.no_read_w)
+            score_s = torch.cat([score_noread, score_yes, score_no, score_s], dim=-1)
         if self.no_answer:
             h0 = dropout(h0, p=dropout_p, training=self.training)
             score_s = torch.cat([score_s, self.get_single_score(x, h0, x_mask, self.noanswer_linear, self.noanswer_w)], dim=-1)
         return F.softmax(score_s, dim=-1)
 
+    def _proj(self, attn, x_part, h0):
+        """attn's projection of h0 with the variational-dropout mask BilinearSeqAttn draws for its x (one (B, D) mask per call, :454-455)
+        folded in - (x o m) . u == x . (m o u) -, drawn in the unfused order: the mask of x, then the dropout of h0."""
+        m = seq_dropout_mask(x_part, p=dropout_p, training=self.training)
+        u = ops.linear(dropout(h0, p=dropout_p, training=self.training), attn.linear.weight, attn.linear.bias)
+        return u if m is None else u * m
+
     def _forward_fused(self, x, h0, x_mask, ES_len, mask_flag):
         """The same computation with the (B, L, D) work in ONE kernel per direction (ops.fused_scorer).  The three projections of h0 stay
-        small GEMMs; the variational-dropout masks BilinearSeqAttn draws for its x (one (B, D) mask per call, :456-457) are folded into
-        the projected vectors - (x o m) . u == x . (m o u) - in the order the unfused code draws them (attn, then attn2)."""
-        def proj(attn, x_part):
-            m = seq_dropout_mask(x_part, p=dropout_p, training=self.training)          # the call's dropout of x
-            u = ops.linear(dropout(h0, p=dropout_p, training=self.training), attn.linear.weight, attn.linear.bias)
-            return u if m is None else u * m
-        u1 = proj(self.attn, x[:, ES_len:])
-        u2 = proj(self.attn2, x[:, :ES_len])
+        small GEMMs, taken in the order the unfused code draws their masks (attn, then attn2, then the no-answer head)."""
+        u1 = self._proj(self.attn, x[:, ES_len:], h0)
+        u2 = self._proj(self.attn2, x[:, :ES_len], h0)
         hd = dropout(h0, p=dropout_p, training=self.training)
         uh = ops.linear(hd, self.noanswer_linear.weight, self.noanswer_linear.bias)
         return ops.fused_scorer(x, u1, u2, uh, self.noanswer_w.weight, self.noanswer_w.bias, x_mask, ES_len, bool(mask_flag))
 
+    def _forward_fused_heads(self, x, h0, x_mask, ES, mask_flag):
+        """``yesno``: the slot scores and the 3 (+1 with no_answer) pooled heads in ONE kernel per direction (ops.fused_scorer_heads),
+        heads ordered no_read, yes, no, noanswer as the columns are (:411, :416).  ES == 0: no ES split (useES off).  Masks and dropouts
+        of h0 are drawn in the unfused order: attn, attn2, the yes/no heads' h0, the no-answer head's h0 (the dropped h0 dropped again)."""
+        B, D = x.size(0), x.size(2)
+        u1 = self._proj(self.attn, x[:, ES:], h0)
+        u2 = self._proj(self.attn2, x[:, :ES], h0) if ES > 0 else None
+        heads = [(self.no_read_linear, self.no_read_w), (self.yes_linear, self.yes_w), (self.no_linear, self.no_w)]
+        hd = dropout(h0, p=dropout_p, training=self.training)
+        # the three projections share one dropped h0: one product over the stacked weights
+        uh = ops.linear(hd, torch.cat([l.weight for l, _ in heads], 0), torch.cat([l.bias for l, _ in heads], 0)).view(B, 3, D)
+        if self.no_answer:
+            hd = dropout(hd, p=dropout_p, training=self.training)
+            uh = torch.cat([uh, ops.linear(hd, self.noanswer_linear.weight, self.noanswer_linear.bias).unsqueeze(1)], 1)
+            heads.append((self.noanswer_linear, self.noanswer_w))
+        w = torch.cat([r.weight for _, r in heads], 0)
+        b = torch.cat([r.bias for _, r in heads], 0)
+        return ops.fused_scorer_heads(x, u1, u2, uh, w, b, x_mask, ES, 3, bool(mask_flag))
+
     def get_single_score(self, x, h, x_mask, linear, w):
-        """:421-432: w . (softmax(mask(x . W h)) . x) + b - one fused-attention launch with a single query row."""
+        """:421-432: w . (softmax(mask(x . W h)) . x) + b - on the device one fused-attention launch with a single query row."""
         Wh = ops.linear(h, linear.weight, linear.bias).unsqueeze(1)
+        if not x.is_cuda:
+            a = F.softmax(Wh.bmm(x.transpose(1, 2)).masked_fill(x_mask.eq(0).unsqueeze(1), float("-inf")), dim=2)
+            return ops.linear(a.bmm(x), w.weight, w.bias).squeeze(2)
         return ops.linear(ops.fused_attention(Wh, x, x, x_mask), w.weight, w.bias).squeeze(2)
 
 

@@ -159,6 +159,50 @@ def fused_scorer(x, u1, u2, uh, w, b, mask, ES, mask_flag):
                               mask.to(torch.uint8).contiguous(), ES, mask_flag)
 
 
+class _FusedScorerHeads(torch.autograd.Function):
+    """probs (B, H + L) = softmax([s_0 .. s_{n_front-1}, x_i . u(i) ..., s_{n_front} .. s_{H-1}]) with H pooled heads
+    s_h = w_h . (softmax(mask(x . uh_h)) . x) + b_h - Models/Layers.py:352-432 with ``yesno`` in one launch per direction
+    (ruart_scorer_heads_fwd / _bwd, csrc/sdnet_scorer.hip).  u1 (B, D) scores the slots i >= ES, u2 the first ES (None with ES == 0)."""
+
+    @staticmethod
+    def forward(ctx, x, u1, u2, uh, w, b, mask, ES, n_front, mask_flag):
+        lib = hip.kernels()
+        for t in (x, u1, uh, w, b) + (() if u2 is None else (u2,)):
+            hip.require_gpu(t, torch.float32)
+        nan_flag.ensure(x.device)
+        B, L, D = x.shape
+        H = uh.shape[1]
+        probs = torch.empty(B, H + L, dtype=torch.float32, device=x.device)
+        a = torch.empty(B, H, L, dtype=torch.float32, device=x.device)
+        lib.ruart_scorer_heads_fwd(x, u1, u1 if u2 is None else u2, uh, w, b, mask, probs, a, B, L, D, int(ES), H, int(n_front),
+                                   int(bool(mask_flag)), hip.stream_ptr())
+        ctx.save_for_backward(x, u1, u2, uh, w, probs, a)
+        ctx.ES, ctx.n_front = int(ES), int(n_front)
+        return probs
+
+    @staticmethod
+    def backward(ctx, gp):
+        lib = hip.kernels()
+        x, u1, u2, uh, w, probs, a = ctx.saved_tensors
+        B, L, D = x.shape
+        H = uh.shape[1]
+        gp = gp.contiguous()
+        gx = torch.empty_like(x)
+        gu1, gu2 = (torch.empty(B, D, dtype=torch.float32, device=x.device) for _ in range(2))
+        guh, gwp = (torch.empty(B, H, D, dtype=torch.float32, device=x.device) for _ in range(2))
+        gbp = torch.empty(B, H, dtype=torch.float32, device=x.device)
+        lib.ruart_scorer_heads_bwd(x, u1, u1 if u2 is None else u2, uh, w, probs, a, gp, gx, gu1, gu2, guh, gwp, gbp, B, L, D, ctx.ES, H,
+                                   ctx.n_front, hip.stream_ptr())
+        return gx, gu1, (None if u2 is None else gu2), guh, colsum(gwp.view(B, H * D)).view_as(w), gbp.sum(0), None, None, None, None
+
+
+def fused_scorer_heads(x, u1, u2, uh, w, b, mask, ES, n_front, mask_flag):
+    """x (B, L, D), u1 / u2 (B, D) (u2 None with ES == 0), uh (B, H, D), w (H, D), b (H,), mask (B, L): see _FusedScorerHeads and the
+    argument contract in include/ruart_hip.h; a shape outside it raises ``hip.HipError`` with ``code`` hipErrorInvalidValue (1)."""
+    return _FusedScorerHeads.apply(x.contiguous(), u1.contiguous(), None if u2 is None else u2.contiguous(), uh.contiguous(), w.contiguous(),
+                                   b.contiguous(), mask.to(torch.uint8).contiguous(), ES, n_front, mask_flag)
+
+
 # ---------------------------------------------------------------------------------------------------------
 class _WholeLayerNorm(torch.autograd.Function):
     """F.layer_norm(x, x.size()) - normalisation over the WHOLE tensor, no affine (Models/Layers.py:167-168)."""

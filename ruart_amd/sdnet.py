@@ -1,7 +1,8 @@
 """``SDNet`` - drop-in for the reference's model class (Models/SDNet.py:20-437) on MI355X.
 
 Same constructor signature ``SDNet(opt, embedding)``, same ``forward(q_list, ocr_list, od_list, return_score=False)
--> (score_s (B, max_ocr_num + 1), None)``, same sub-module / parameter names (so ``state_dict`` keys match the
+-> (score_s (B, max_ocr_num + 1), None)`` (``label_yesno``: ``(B, 3 + max_ocr_num (+ 1))``, the no_read / yes / no slots in
+front), same sub-module / parameter names (so ``state_dict`` keys match the
 reference's checkpoints), same mutable ``drop_emb`` attribute the trainer flips.
 
 What is different underneath (results identical up to fp32 summation order; BERT in bf16 by default):
@@ -14,7 +15,7 @@ What is different underneath (results identical up to fp32 summation order; BERT
   * the reference's per-op ``assert isnan == 0`` device syncs are one flag check per forward.
 
 Supported configuration: the shipped conf and its simple toggles.  Branches the shipped conf does not enable
-(img_feature, fixed_answers, ES post_process, ModelParallel, PRE_ALIGN_after_rnn, label_yesno, bidirectional
+(img_feature, fixed_answers, ES post_process, ModelParallel, PRE_ALIGN_after_rnn, bidirectional
 multi2one) raise NotImplementedError - they are out of the hot path's scope.
 """
 import os
@@ -39,7 +40,7 @@ if hasattr(torch.autograd.graph, "set_warn_on_accumulate_grad_stream_mismatch"):
 
 _HOST_DELAY_US = ops._HOST_DELAY_US          # timing diagnostics only; refused without RUART_DIAGNOSTICS=1 (ops.py)
 
-_UNSUPPORTED = ("img_feature", "fixed_answers", "ModelParallel", "PRE_ALIGN_after_rnn", "label_yesno", "no_Context_Self_Attention",
+_UNSUPPORTED = ("img_feature", "fixed_answers", "ModelParallel", "PRE_ALIGN_after_rnn", "no_Context_Self_Attention",
                 "no_DeepAttention")
 
 
@@ -260,7 +261,7 @@ class SDNet(nn.Module):
                 pos_out = ctx_final + opt["position_dim"]
         self.ques_merger = LinearSelfAttn(q_final)
         ocr_final = {"cat": ctx_final + pos_out, "atted": pos_out, "original": ctx_final}[opt["pos_att_merge_mod"]]
-        self.get_answer = GetFinalScores(ocr_final, q_final, yesno=False, no_answer="label_no_answer" in opt, useES="useES" in opt)
+        self.get_answer = GetFinalScores(ocr_final, q_final, yesno="label_yesno" in opt, no_answer="label_no_answer" in opt, useES="useES" in opt)
 
     # ------------------------------------------------------------------------------------------------------
     @property

@@ -6,7 +6,7 @@ There is no network on any box, so checkpoints and datasets are synthetic:
   * SDNet weights under the reference's state-dict names (SURVEY.md §8b);
   * batches in the ``VQA_collate_fun`` 5-tuple layout
     (``Utils/VQA_Dataset.py:448-542``): dicts of int64 id matrices, bool masks,
-    python offset / count lists, ``position (B, max_num, 8)`` and ``gt (B, No+1)``.
+    python offset / count lists, ``position (B, max_num, 8)`` and ``gt (B, No+1)`` (``label_yesno``: ``(B, 3+No(+1))``).
 
 Everything is drawn from ``numpy.random.default_rng(seed)`` in a fixed order so the
 build container (golden generator) and the GPU box regenerate identical arrays.
@@ -170,6 +170,13 @@ def sdnet_param_shapes(opt):
     s["get_answer.rnn.bias_hh"] = (3 * hs,)
     s["get_answer.attn2.linear.weight"] = (xs, hs)
     s["get_answer.attn2.linear.bias"] = (xs,)
+    if "label_yesno" in opt:
+        # after every existing entry: make_sdnet_weights draws in this order, so the weights of a conf without the key do not move
+        for head in ("no", "yes", "no_read"):
+            s["get_answer.%s_linear.weight" % head] = (xs, hs)
+            s["get_answer.%s_linear.bias" % head] = (xs,)
+            s["get_answer.%s_w.weight" % head] = (1, xs)
+            s["get_answer.%s_w.bias" % head] = (1,)
     return s
 
 
@@ -319,9 +326,12 @@ def synthetic_batch(opt, B, seed=7, n_q=30, n_ocr=100, n_od=None, bert_vocab=305
 
     gt = None
     if targets:
-        gt = torch.zeros(B, opt["max_ocr_num"] + 1)
+        front = 3 if "label_yesno" in opt else 0          # no_read / yes / no in front of the OCR slots (dataset.py)
+        gt = torch.zeros(B, front + opt["max_ocr_num"] + (1 if front == 0 or "label_no_answer" in opt else 0))
         for b in range(B):
-            gt[b, int(g.integers(0, max(1, ocr["num_cnt"][b] - 1)))] = 1.0
+            k = int(g.integers(0, max(1, ocr["num_cnt"][b] - 1)))
+            # label_yesno: every second sample's answer is one of the three front slots
+            gt[b, k % 3 if front and b % 2 else front + k] = 1.0
     extra = [{"q_id": b, "answers": None,
               "ocr_list": ["w%d" % k for k in range(ocr["num_cnt"][b] - 1)] + ["<OCR>"],
               "image_path": "synthetic/%d.jpg" % b} for b in range(B)]

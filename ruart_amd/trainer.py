@@ -144,6 +144,50 @@ def decode_predictions(scores, num_cnt, extra_info, opt):
     return ANLS, ACC, res, save_res
 
 
+_FRONT_ANSWERS = ("answering does not require reading text in the image", "yes", "no")
+
+
+def decode_slots(scores, num_cnt, extra_info, opt):
+    """``decode_predictions`` for the layout of ``label_yesno``: scores (B, 3 + n_ocr_slots (+ 1)) with the no_read / yes / no slots in
+    front (Models/SDNetTrainer.py:396-448 with fixed_answers_len = 0, yesno_num = 3), again as one masked arg-max on the device.
+    A slot is admissible when idx < 3 + num_cnt - or it is the no-answer slot (last column, ``label_no_answer``), where the walk stops
+    first - and idx != len(ocr_list) - 1.  Both of the reference's quirks are kept (sic): that sentinel test is not offset by the three
+    front slots, so slot len(ocr_list) - 1 - a real OCR item (or a front slot) - is skipped, and slot 3 + num_cnt - 1, the ``<OCR>``
+    sentinel itself, is admissible and decodes to "<OCR>".  Nothing admissible: the lowest-scored slot, as in ``decode_predictions``."""
+    from .metrics import note_stvqa, note_textvqa
+    if "fixed_answers" in opt:
+        raise NotImplementedError("fixed-answer slots are outside the accelerated path (SURVEY section 8)")
+    front = len(_FRONT_ANSWERS)
+    B, n_slots = scores.shape
+    no_answer = "label_no_answer" in opt
+    cnt = torch.as_tensor(list(num_cnt), device=scores.device)
+    skipped = torch.as_tensor([len(e["ocr_list"]) - 1 for e in extra_info], device=scores.device)
+    ar = torch.arange(n_slots, device=scores.device).unsqueeze(0)
+    valid = (ar < front + cnt.unsqueeze(1)) & (ar != skipped.unsqueeze(1))
+    if no_answer:
+        valid[:, -1] = True                      # (tested before the skip: the walk stops there even when it is the skipped index)
+    best = scores.masked_fill(~valid, -1.0).argmax(dim=1)
+    idxs = torch.where(valid.any(dim=1), best, scores.argmin(dim=1)).cpu().tolist()
+    prob = scores.detach().cpu()
+    res, save_res, ANLS, ACC = [], [], 0, 0
+    for i, idx in enumerate(idxs):
+        if idx < front:
+            answer = _FRONT_ANSWERS[idx]
+        elif idx < front + int(num_cnt[i]):
+            answer = extra_info[i]["ocr_list"][idx - front]
+        else:
+            answer = "unanswerable"
+        res.append({"question_id": extra_info[i]["q_id"], "answer": answer})
+        save_res.append({"question_id": extra_info[i]["q_id"], "prediction": answer, "answers": extra_info[i]["answers"],
+                         "score": prob[i, idx].item(), "idx": idx, "ids_len": n_slots, "ocr_list": extra_info[i]["ocr_list"]})
+        if extra_info[i]["answers"] is not None:
+            a = note_stvqa(extra_info[i]["answers"], answer)
+            c = note_textvqa(extra_info[i]["answers"], answer)
+            ACC += min(c * 10 / 3.0, 1) if len(extra_info[i]["answers"]) == 10 else min(c * 10, 1)
+            ANLS += a if a >= 0.5 else 0
+    return ANLS, ACC, res, save_res
+
+
 class BaseTrainer:
     """Models/BaseTrainer.py:6-69: option plumbing, the feature folder, the run folder."""
 
@@ -545,7 +589,8 @@ class SDNetTrainer(BaseTrainer):
             scores, _ = self.network(q_list, ocr_list, od_list)
             loss = self.loss_func(scores, gt_list).item() if gt_list is not None else 0
         self.network.check_nan()
-        ANLS, ACC, res, save_res = decode_predictions(scores, ocr_list["num_cnt"], extra_info, self.opt)
+        decode = decode_slots if "label_yesno" in self.opt else decode_predictions
+        ANLS, ACC, res, save_res = decode(scores, ocr_list["num_cnt"], extra_info, self.opt)
         return loss, ANLS, ACC, res, save_res
 
     def _is_main(self):
