@@ -290,6 +290,11 @@ def _sort_ids(ids, padding_idx=None, max_seg=64):
     return order.astype(np.int32), sub_start.astype(np.int32), row_first.astype(np.int32), sid[starts].astype(np.int32)
 
 
+def es_post_len(opt):
+    """ES_ocr_len when the conf selects ``ES_using_way post_process`` (Models/SDNet.py:246, 292), else 0."""
+    return int(opt["ES_ocr_len"]) if ("ES_ocr" in opt and opt.get("ES_using_way") == "post_process") else 0
+
+
 class BatchIndex:
     """Everything ``SDNet.forward`` needs besides the reference's own batch tensors.
 
@@ -303,6 +308,24 @@ class BatchIndex:
         self.od = ItemIndex(od_list, wk_o, od_list["position"].size(1))
         self.device = None
         self.ocr_mask = self.od_mask = None
+        # ES_using_way post_process (Models/SDNet.py:292-324): the first E slots of the item matrix are the ES part, the trunk runs on
+        # the other No - E.  Row indices of the two parts in the flat (B * No, D) item matrix, the (B, No - E) trunk mask, the scorer
+        # mask [ones (B, E) | trunk mask] and the positions of the trunk's slots (a copy: the caller's dict keeps its tensor).
+        # Host arrays only so far, pinned against the reference (tests/golden/es_post_masks.npz): SDNet still refuses the conf, and
+        # nothing is shipped to the device for it.
+        self.es_post = es_post_len(opt)
+        if self.es_post:
+            E, No, B = self.es_post, self.ocr.max_num, self.ocr.B
+            if not 0 < E < No:
+                raise ValueError("ES_using_way post_process: ES_ocr_len %d needs 0 < ES_ocr_len < %d position rows" % (E, No))
+            rows = np.arange(B * No, dtype=np.int64).reshape(B, No)
+            self.es_rows, self.trunk_rows = rows[:, :E].reshape(-1), rows[:, E:].reshape(-1)
+            cnt = self.ocr.num_cnt
+            # (sic) :313-318: a sample with fewer than E items keeps its whole count as live trunk slots
+            live = np.where(cnt >= E, cnt - E, cnt)
+            self.trunk_mask = (np.arange(No - E)[None, :] < live[:, None]).astype(np.uint8)
+            self.score_mask = np.concatenate([np.ones((B, E), dtype=np.uint8), self.trunk_mask], 1)
+            self.trunk_pos = ocr_list["position"][:, E:].contiguous()
         # BERT: one packed pass over question + OCR items + object items, and the pooling descriptors
         self.packed = None
         self.spans = None

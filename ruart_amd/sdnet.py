@@ -14,9 +14,9 @@ What is different underneath (results identical up to fp32 summation order; BERT
   * every LSTM recurrence, attention score/softmax/context and whole-tensor layer norm is a HIP kernel (ops.py);
   * the reference's per-op ``assert isnan == 0`` device syncs are one flag check per forward.
 
-Supported configuration: the shipped conf and its simple toggles.  Branches the shipped conf does not enable
-(img_feature, fixed_answers, ES post_process, ModelParallel, PRE_ALIGN_after_rnn, bidirectional
-multi2one) raise NotImplementedError - they are out of the hot path's scope.
+Supported configuration: the shipped conf, its simple toggles and the trunk ablation ``no_Context_Self_Attention``.  Other
+branches the shipped conf does not enable (img_feature, fixed_answers, ES post_process, ModelParallel, PRE_ALIGN_after_rnn,
+bidirectional multi2one) raise NotImplementedError - they are out of the hot path's scope.
 """
 import os
 
@@ -40,8 +40,7 @@ if hasattr(torch.autograd.graph, "set_warn_on_accumulate_grad_stream_mismatch"):
 
 _HOST_DELAY_US = ops._HOST_DELAY_US          # timing diagnostics only; refused without RUART_DIAGNOSTICS=1 (ops.py)
 
-_UNSUPPORTED = ("img_feature", "fixed_answers", "ModelParallel", "PRE_ALIGN_after_rnn", "no_Context_Self_Attention",
-                "no_DeepAttention")
+_UNSUPPORTED = ("img_feature", "fixed_answers", "ModelParallel", "PRE_ALIGN_after_rnn", "no_DeepAttention")
 
 
 def _record(t, stream):
@@ -81,9 +80,9 @@ class _Trunk(nn.Module):
         super().__init__()
         self.opt = net.opt
         for name in ("ques_rnn", "high_lvl_ques_rnn", "ques_self_attn", "ques_merger", "context_rnn", "deep_attn",
-                     "highlvl_self_att", "high_lvl_context_rnn", "get_answer"):
+                     "high_lvl_context_rnn", "get_answer"):
             setattr(self, name, getattr(net, name))
-        for name in ("od_ocr_attn", "position_attn"):
+        for name in ("highlvl_self_att", "od_ocr_attn", "position_attn"):
             if hasattr(net, name):
                 setattr(self, name, getattr(net, name))
         self._net_streams = net._side_streams       # eager mode shares the SDNet's two side streams (few HW queues)
@@ -135,6 +134,8 @@ class _Trunk(nn.Module):
                     for t in q_rnn_layers:
                         _record(t, torch.cuda.current_stream(dev))
                 h, pre = self.deep_attn([x], rnn_layers, q_long, q_rnn_layers, mask, q_mask, return_bef_rnn=True, helper=helper)
+                if "no_Context_Self_Attention" in opt:                          # SDNet.py:383-385
+                    return self.high_lvl_context_rnn(h, mask, LN=True, ln_group=ln_group)
                 sa_in = torch.cat([h, pre, x], 2)
                 sa = self.highlvl_self_att(sa_in, sa_in, mask, x3=h)
                 return self.high_lvl_context_rnn(torch.cat([h, sa], 2), mask, LN=True, ln_group=ln_group)
@@ -169,6 +170,9 @@ class SDNet(nn.Module):
             raise NotImplementedError("ES_using_way post_process is outside the accelerated hot path")
         if opt.get("multi2one_bidir"):
             raise NotImplementedError("bidirectional multi2one is outside the accelerated hot path")
+        if opt.get("ruart_graph_trunk", False) and "no_Context_Self_Attention" in opt:
+            # the captured trunk was never run in this form: refused rather than served unverified
+            raise NotImplementedError("opt['ruart_graph_trunk'] serves the trunk with the context self-attention only")
         self.opt = opt
         self.vocab_dim = 300
         self.use_cuda = opt.get("cuda") is True
@@ -245,9 +249,13 @@ class SDNet(nn.Module):
                                                       num_layers=opt["question_high_lvl_rnn_layers"], concat_rnn=True)
         self.after_deep_attn_size = self.deep_attn_output_size + self.deep_attn_input_size + m2o
         self.self_attn_input_size = self.after_deep_attn_size
-        self.highlvl_self_att = Attention(self.self_attn_input_size, opt["deep_att_hidden_size_per_abstr"], correlation_func=3)
-        self.high_lvl_context_rnn, ctx_final = RNN_from_opt(self.deep_attn_output_size * 2, opt["highlvl_hidden_size"], num_layers=1,
-                                                            concat_rnn=False)
+        if "no_Context_Self_Attention" in opt:          # SDNet.py:180-188: the high-level RNN reads deep_attn's hidden output alone
+            self_attn_out = 0
+        else:
+            self.highlvl_self_att = Attention(self.self_attn_input_size, opt["deep_att_hidden_size_per_abstr"], correlation_func=3)
+            self_attn_out = self.deep_attn_output_size
+        self.high_lvl_context_rnn, ctx_final = RNN_from_opt(self.deep_attn_output_size + self_attn_out, opt["highlvl_hidden_size"],
+                                                            num_layers=1, concat_rnn=False)
         self.ques_self_attn = Attention(hq_out, opt["query_self_attn_hidden_size"], correlation_func=3)
         q_final = hq_out
         pos_out = 0

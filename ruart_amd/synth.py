@@ -116,6 +116,8 @@ def sdnet_dims(opt):
 
 
 def sdnet_param_shapes(opt):
+    """name -> shape, in the order make_sdnet_weights draws.  Always the table WITH the context self-attention: the conf key
+    ``no_Context_Self_Attention`` is applied by make_sdnet_weights to what it drew, so that it moves no other tensor."""
     d = sdnet_dims(opt)
     V = int(opt["vocab_size"])
     s = {}
@@ -177,13 +179,21 @@ def sdnet_param_shapes(opt):
             s["get_answer.%s_linear.bias" % head] = (xs,)
             s["get_answer.%s_w.weight" % head] = (1, xs)
             s["get_answer.%s_w.bias" % head] = (1,)
+    if "ES_ocr" in opt and opt.get("ES_using_way") == "post_process":      # Models/SDNet.py:246-248; again after every earlier entry
+        s["ES_linear.weight"] = (xs, d["m2o"])
+        s["ES_linear.bias"] = (xs,)
+        attn("ES_ocr_att", xs, d["h"], True)
     return s
 
 
 def make_sdnet_weights(opt, seed=1033):
-    """name -> float32 array for every entry of sdnet_param_shapes(opt)."""
+    """name -> float32 array for every entry of sdnet_param_shapes(opt).  ``no_Context_Self_Attention`` (Models/SDNet.py:180-188)
+    draws that table too and then drops the self-attention's tensors and keeps the first columns of the narrower
+    ``high_lvl_context_rnn`` input weights (the ones that multiply deep_attn's output in either form): every other tensor is the one
+    the conf without the key gets."""
     g = np.random.default_rng(seed + 17)
     out = {}
+    no_ctx = "no_Context_Self_Attention" in opt
     for name, shape in sdnet_param_shapes(opt).items():
         if name == "alphaBERT":
             a = 1.0 + 0.5 * g.standard_normal(shape)
@@ -207,6 +217,10 @@ def make_sdnet_weights(opt, seed=1033):
             else:
                 k = 0.05
             a = g.uniform(-k, k, shape)
+        if no_ctx and name.startswith("highlvl_self_att."):
+            continue
+        if no_ctx and name.startswith("high_lvl_context_rnn.") and "weight_ih" in name:
+            a = a[:, :shape[1] // 2]
         out[name] = np.ascontiguousarray(a, dtype=np.float32)
     return out
 
