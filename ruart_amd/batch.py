@@ -248,15 +248,17 @@ class ItemIndex:
         self.mask = mask
         self.dev = None
         self.emb_sort = {}
+        self.extra = {}                # further int64 vectors shipped with the fields (BatchIndex: the image-feature overlay rows)
 
     _FIELDS = ("item_of_word", "sample_of_word", "tok_in_sample", "step_rows", "sorted_sample", "sorted_slot", "flat_word", "flat_tok",
                "flat_slot")
 
     def fields(self):
-        return list(self._FIELDS) + ["ids_" + k for k in sorted(self.word_ids)]
+        return list(self._FIELDS) + ["ids_" + k for k in sorted(self.word_ids)] + sorted(self.extra)
 
     def pack_host(self):
-        return [getattr(self, f).astype(np.int64) for f in self._FIELDS] + [self.word_ids[k] for k in sorted(self.word_ids)]
+        return [getattr(self, f).astype(np.int64) for f in self._FIELDS] + [self.word_ids[k] for k in sorted(self.word_ids)] \
+            + [self.extra[k].astype(np.int64) for k in sorted(self.extra)]
 
     def bind(self, tensors):
         self.dev = dict(zip(self.fields(), tensors))
@@ -290,6 +292,16 @@ def _sort_ids(ids, padding_idx=None, max_seg=64):
     return order.astype(np.int32), sub_start.astype(np.int32), row_first.astype(np.int32), sid[starts].astype(np.int32)
 
 
+def img_feature_form(opt):
+    """None, "overlay" or "pure": how the conf lays region image features under the object branch (Models/SDNet.py:276-307).
+    ``img_feature`` makes ``od_input`` the projected features, (B, img_fea_num, .), every row live.  Without the further key
+    ``img_feature_replace_od`` the object items' last states are then written over the first rows of each sample (the loop guard of
+    :301 tests that other key): the overlay form.  With it the object items contribute nothing: the pure form."""
+    if "img_feature" not in opt:
+        return None
+    return "pure" if "img_feature_replace_od" in opt else "overlay"
+
+
 def es_post_len(opt):
     """ES_ocr_len when the conf selects ``ES_using_way post_process`` (Models/SDNet.py:246, 292), else 0."""
     return int(opt["ES_ocr_len"]) if ("ES_ocr" in opt and opt.get("ES_using_way") == "post_process") else 0
@@ -305,7 +317,21 @@ class BatchIndex:
     def __init__(self, q_list, ocr_list, od_list, opt, device=None, bert=None, pack=None, mfma_long=None):
         wk_o, wk_q = opt["ocr_emb_initial"], opt["q_emb_initial"]
         self.ocr = ItemIndex(ocr_list, wk_o, ocr_list["position"].size(1))
-        self.od = ItemIndex(od_list, wk_o, od_list["position"].size(1))
+        # region image features (img_feature_form): the object branch is (B, img_fea_num, .) with every row live.  Overlay form: the
+        # object items are encoded as ever and their last states land on rows b * img_fea_num + k of the projected features - one flat
+        # index of distinct rows (``flat_img``, in multi2one's item order like flat_slot).  Pure form: the reference encodes the object
+        # items and throws the result away; here they are not indexed, embedded or put into the encoder stream at all (``self.od`` None).
+        self.img_form = img_feature_form(opt)
+        self.od = None if self.img_form == "pure" else ItemIndex(od_list, wk_o, od_list["position"].size(1))
+        if self.img_form is not None:
+            n_img = int(opt["img_fea_num"])
+            if self.od is not None:
+                over = np.flatnonzero(self.od.num_cnt > n_img)
+                if len(over):
+                    raise ValueError("sample %d holds %d object items, img_fea_num is %d: the image-feature overlay has no row for them"
+                                     % (int(over[0]), int(self.od.num_cnt[over[0]]), n_img))
+                self.od.extra["flat_img"] = self.od.sorted_sample * n_img + self.od.sorted_slot
+            self.img_od_mask = np.ones((self.ocr.B, n_img), dtype=np.uint8)
         self.device = None
         self.ocr_mask = self.od_mask = None
         # ES_using_way post_process (Models/SDNet.py:292-324): the first E slots of the item matrix are the ES part, the trunk runs on
@@ -342,13 +368,17 @@ class BatchIndex:
             # bit-neutral; opt['bert_dedup'] / opt['bert_last_rows'] = False switch them off)
             frozen = "LOCK_BERT" in opt and not opt.get("bert_frozen_dropout")
             dedup = frozen and bool(opt.get("bert_dedup", True)) and bool(pack)
-            self.plan = (bool(pack), bool(mfma_long), dedup)
-            groups = [(q_list["bert"], q_list["bert_mask"]), (ocr_list["bert"], ocr_list["bert_mask"]), (od_list["bert"], od_list["bert_mask"])]
+            self.plan = (bool(pack), bool(mfma_long), dedup) + (("no_od_group",) if self.od is None else ())
+            groups = [(q_list["bert"], q_list["bert_mask"]), (ocr_list["bert"], ocr_list["bert_mask"])]
+            item_groups = [(q_list, wk_q), (ocr_list, wk_o)]
+            if self.od is not None:
+                groups.append((od_list["bert"], od_list["bert_mask"]))
+                item_groups.append((od_list, wk_o))
             self.packed = PackedTokens(groups, None, pack=pack, mfma_long=mfma_long, dedup=dedup)
             if "LOCK_BERT" not in opt:
                 self.packed.prepare_embedding_sorts()      # trainable encoder: its embedding gradients take the sorted, ordered path
             spans = []
-            for g, (items, wk) in enumerate(((q_list, wk_q), (ocr_list, wk_o), (od_list, wk_o))):
+            for g, (items, wk) in enumerate(item_groups):
                 wm = _np(items[wk + "_mask"])
                 arr = items.get("_bert_offsets_arr")          # attached by the collate's fast path
                 if arr is None:
@@ -403,6 +433,8 @@ class BatchIndex:
         for k in q_keys:
             self._emb_host[("q", k)] = _sort_ids(_np(q_list[k]).reshape(-1), 1 if k in ("glove", "fasttext", "phoc") else None)
         for name, items, idx in (("ocr", ocr_list, self.ocr), ("od", od_list, self.od)):
+            if idx is None:
+                continue
             for k in ("glove", "fasttext", "phoc", "pos", "ent"):
                 if k in items and isinstance(items[k], torch.Tensor):
                     self._emb_host[(name, k)] = _sort_ids(_np(items[k]).reshape(-1)[idx.flat_word],
@@ -415,10 +447,11 @@ class BatchIndex:
     def _staged(self):
         h = self.__dict__.get("_h")
         if h is None:
-            items = self.ocr.pack_host() + self.od.pack_host()
+            items = self.ocr.pack_host() + (self.od.pack_host() if self.od is not None else [])
             h = {"item_sizes": [len(a) for a in items],
                  "items": torch.from_numpy(np.concatenate(items)) if sum(len(a) for a in items) else torch.zeros(0, dtype=torch.long),
-                 "ocr_mask": torch.from_numpy(self.ocr.mask), "od_mask": torch.from_numpy(self.od.mask)}
+                 "ocr_mask": torch.from_numpy(self.ocr.mask),
+                 "od_mask": torch.from_numpy(self.od.mask if self.img_form is None else self.img_od_mask)}
             if self._emb_host:
                 h["emb"] = torch.from_numpy(np.concatenate([np.concatenate(self._emb_host[k]) for k in self._emb_host]).astype(np.int32))
             if self.packed is not None:
@@ -445,7 +478,8 @@ class BatchIndex:
         parts = list(torch.split(buf, h["item_sizes"]))
         n = len(self.ocr.fields())
         self.ocr.bind(parts[:n])
-        self.od.bind(parts[n:])
+        if self.od is not None:
+            self.od.bind(parts[n:])
         self.ocr_mask = h["ocr_mask"].to(self.device, non_blocking=True)
         self.od_mask = h["od_mask"].to(self.device, non_blocking=True)
         if self._emb_host:
@@ -459,7 +493,8 @@ class BatchIndex:
                     o += len(a)
                 self.emb_sort[k] = tuple(parts)
             self.ocr.emb_sort = {k[1]: v for k, v in self.emb_sort.items() if k[0] == "ocr"}
-            self.od.emb_sort = {k[1]: v for k, v in self.emb_sort.items() if k[0] == "od"}
+            if self.od is not None:
+                self.od.emb_sort = {k[1]: v for k, v in self.emb_sort.items() if k[0] == "od"}
         if self.packed is not None:
             self.packed.bind(self.device, h["packed"])
             shapes = self._spans_host[1]

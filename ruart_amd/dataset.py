@@ -10,8 +10,11 @@ Reference: ``Utils/VQA_Dataset.py:13-437`` (dataset), ``Utils/CoQAPreprocess.py:
 which ``batch.VQA_collate`` turns into the 5-tuple the model takes.  Everything here is integer / string work on the host and is
 pinned bit-exact against the reference's own class on a synthetic record set (``tests/golden/dataset_*.json``).
 
-Not carried over (outside SURVEY section 8): the ``DEBUG`` length histograms, grid image features (``img_feature``) and the
-fixed-answer vocabulary (``fixed_answers``) - asking for them raises."""
+With ``img_feature`` the question dict also carries ``img_features (1, 36, 2048)`` / ``img_spatials (1, 36, 8)`` from a ready table or
+from per-image files (``get_image_feature``, pinned against the reference in ``tests/golden/img_feature_dataset.npz``).
+
+Not carried over (outside SURVEY section 8): the ``DEBUG`` length histograms and the fixed-answer vocabulary (``fixed_answers``,
+which raises)."""
 import itertools
 import logging
 import os
@@ -76,12 +79,14 @@ def flatten_items(items):
 class VQA_Dataset(Dataset):
     def __init__(self, data, opt, mode="train", image_features=None, fixed_answers_entry=None):
         assert mode in ("train", "dev", "test")
-        if "img_feature" in opt or image_features is not None:
-            raise NotImplementedError("grid image features are outside the accelerated path (SURVEY section 8)")
         if "fixed_answers" in opt or fixed_answers_entry is not None:
-            raise NotImplementedError("the fixed-answer vocabulary is outside the accelerated path (SURVEY section 8)")
+            raise NotImplementedError("the fixed-answer vocabulary cannot run in the reference's model (sdnet._check_img_feature)")
         self.opt = opt
         self.mode = mode
+        # region image features (``img_feature``): a ready table {'img_id2idx', 'img_features', 'img_spatials'} - what the reference's
+        # trainer reads from hdf5 - or, without one, per-image files under opt['img_fea_folder'] (get_image_feature)
+        self.image_features = image_features
+        self.img_features_cache = {}
         dropped = []
         self.data = []
         for datum in data:                               # VQA_Dataset.py:19-27: no question words, or no answers outside test
@@ -125,6 +130,8 @@ class VQA_Dataset(Dataset):
         od_items = self.get_list_from_datum(datum, self.od_name_list, od_ocr="od", remove_same=dedup)
         datum["annotated_question"]["original"] = datum["question"].lower()
         q = self.get_item_embedding(datum["annotated_question"], self.q_embedding)
+        if "img_feature" in self.opt:                    # VQA_Dataset.py:143-144
+            q["img_features"], q["img_spatials"] = self.get_image_feature(datum["filename"], datum["question_id"])
         ocr_items = ocr_items[:self.max_ocr_num]
         od_items = od_items[:self.max_od_num]
         answers = datum.get("orign_answers")
@@ -178,6 +185,47 @@ class VQA_Dataset(Dataset):
                 "ent": (np.array(ent, dtype=np.int64), len_e), "bert": (np.array(bert, dtype=np.int64), len_b),
                 "bert_offsets": (np.array(offs, dtype=np.int64).reshape(-1, 2), len_o),
                 "position": np.asarray(position, dtype=np.float32).reshape(n, 8)}
+
+    # -- region image features (VQA_Dataset.py:154-207) ---------------------------------------------------------
+    @staticmethod
+    def _corners(bbox):
+        """(n, 4) boxes x0 y0 x1 y1 -> (1, n, 8) float32 corner layout x0 y0 x1 y0 x1 y1 x0 y1, the layout of the items' ``position``."""
+        spa = torch.zeros(1, bbox.size(0), 8)
+        for col, src in enumerate((0, 1, 2, 1, 2, 3, 0, 3)):
+            spa[0, :, col] = bbox[:, src]
+        return spa
+
+    def get_image_feature(self, image_path, q_id):
+        """-> (img_features (1, n, D), img_spatials (1, n, 8)), with the reference's quirks.
+        Table: ``q_id`` must be a key of ``img_id2idx``, but the two tables are indexed by ``q_id`` itself (sic, :156-159); the shapes
+        are asserted to be (1, 36, 2048) / (1, 36, 8).  Folder: ``<img_fea_folder>/{train|test}/<name>.npy`` and ``<name>_info.npy``
+        (a pickled dict: bbox, image_width, image_height), where <name> is the path's dot-separated parts without the last, joined
+        WITHOUT the dots (sic, :177: ``a.b/c.jpg`` -> ``ab/c``); the box is divided by width / height in its own dtype and then stored
+        as float32; results are cached per image path."""
+        if self.image_features is not None:
+            self.image_features["img_id2idx"][q_id]          # (sic) looked up and not used: a KeyError for an unknown question id
+            img_fea = self.image_features["img_features"][q_id].unsqueeze(0)
+            img_spa = self._corners(self.image_features["img_spatials"][q_id])
+            assert img_fea.size() == (1, 36, 2048)
+            assert img_spa.size() == (1, 36, 8)
+            return img_fea, img_spa
+        hit = self.img_features_cache.get(image_path)
+        if hit is not None:
+            return hit
+        name = "".join(image_path.split(".")[:-1])
+        folder = os.path.join(self.opt["img_fea_folder"], "train" if self.mode != "test" else "test")
+        fea_path, info_path = os.path.join(folder, name + ".npy"), os.path.join(folder, name + "_info.npy")
+        assert os.path.exists(fea_path), fea_path
+        img_fea = torch.from_numpy(np.load(fea_path)).unsqueeze(0)
+        assert os.path.exists(info_path), info_path
+        info = np.load(info_path, allow_pickle=True).item()
+        bbox = torch.from_numpy(info["bbox"])
+        bbox[:, 0] = bbox[:, 0] / info["image_width"]
+        bbox[:, 2] = bbox[:, 2] / info["image_width"]
+        bbox[:, 1] = bbox[:, 1] / info["image_height"]
+        bbox[:, 3] = bbox[:, 3] / info["image_height"]
+        hit = self.img_features_cache[image_path] = (img_fea, self._corners(bbox))
+        return hit
 
     # -- candidate lists (VQA_Dataset.py:293-349) ---------------------------------------------------------------
     def get_list_from_datum(self, datum, name_list, od_ocr="ocr", remove_same=False):

@@ -14,9 +14,13 @@ What is different underneath (results identical up to fp32 summation order; BERT
   * every LSTM recurrence, attention score/softmax/context and whole-tensor layer norm is a HIP kernel (ops.py);
   * the reference's per-op ``assert isnan == 0`` device syncs are one flag check per forward.
 
-Supported configuration: the shipped conf, its simple toggles and the trunk ablation ``no_Context_Self_Attention``.  Other
-branches the shipped conf does not enable (img_feature, fixed_answers, ES post_process, ModelParallel, PRE_ALIGN_after_rnn,
-bidirectional multi2one) raise NotImplementedError - they are out of the hot path's scope.
+Supported configuration: the shipped conf, its simple toggles (the embedding sets, ``position_mod`` / ``pos_att_merge_mod``,
+``label_yesno``, a trained encoder), the trunk ablation ``no_Context_Self_Attention`` and region image features in the one way the
+reference can run them: ``img_feature`` with ``img_fea_way replace_od``, laid under the object items (the overlay form) or, with
+``img_feature_replace_od``, in their place (the pure form, whose encoder stream carries no object items; batch.img_feature_form).
+Refused with NotImplementedError: ``img_fea_way final_att`` (the reference builds ``get_answer`` for 3 * ques_final_size and hands it
+ques_final_size: it cannot run), ``fixed_answers`` (its ``fixed_ocr_alpha`` exists under ``final_att`` only), ``ES_using_way
+post_process`` (host index only so far), ModelParallel, PRE_ALIGN_after_rnn, no_DeepAttention and a bidirectional multi2one.
 """
 import os
 
@@ -27,7 +31,7 @@ import torch.nn.functional as F
 from . import hip
 from . import layers as L
 from . import ops
-from .batch import BatchIndex
+from .batch import BatchIndex, img_feature_form
 from .bert import Bert, _PoolMix, bert_encode
 from . import bert_train
 from .layers import Attention, DeepAttention, GetFinalScores, LinearSelfAttn, RNN_from_opt, dropout, row_dropout
@@ -40,7 +44,30 @@ if hasattr(torch.autograd.graph, "set_warn_on_accumulate_grad_stream_mismatch"):
 
 _HOST_DELAY_US = ops._HOST_DELAY_US          # timing diagnostics only; refused without RUART_DIAGNOSTICS=1 (ops.py)
 
-_UNSUPPORTED = ("img_feature", "fixed_answers", "ModelParallel", "PRE_ALIGN_after_rnn", "no_DeepAttention")
+_UNSUPPORTED = ("ModelParallel", "PRE_ALIGN_after_rnn", "no_DeepAttention")
+
+
+def _check_img_feature(opt):
+    """The image-feature conf keys, checked before anything is allocated (Models/SDNet.py:221-240)."""
+    if "fixed_answers" in opt:
+        # Models/SDNet.py:432-436 scales the fixed-answer logits by fixed_ocr_alpha, a parameter only img_fea_way final_att creates (:236)
+        raise NotImplementedError("conf key 'fixed_answers' cannot run in the reference: its forward reads fixed_ocr_alpha, which exists "
+                                  "only under img_fea_way final_att - and that way cannot run either")
+    if "img_feature" not in opt:
+        return
+    way = opt.get("img_fea_way")
+    if way != "replace_od":
+        raise NotImplementedError("img_fea_way %r: only 'replace_od' runs in the reference - under 'final_att' it builds get_answer for "
+                                  "3 * ques_final_size (Models/SDNet.py:238-242) and hands it q_merged of ques_final_size (:429-431)" % (way,))
+    for k in ("img_fea_num", "img_fea_dim", "img_spa_dim"):
+        if k not in opt:
+            raise KeyError("conf key %r is required with img_feature" % k)
+    if "position_dim" in opt and int(opt["img_spa_dim"]) != int(opt["position_dim"]):
+        raise ValueError("img_spa_dim %d != position_dim %d: the image boxes take the object positions' place in the position attention"
+                         % (int(opt["img_spa_dim"]), int(opt["position_dim"])))
+    if opt.get("ruart_graph_trunk", False):
+        # the captured trunk was never run in this form: refused rather than served unverified
+        raise NotImplementedError("opt['ruart_graph_trunk'] was never run with img_feature")
 
 
 def _record(t, stream):
@@ -166,6 +193,7 @@ class SDNet(nn.Module):
         for k in _UNSUPPORTED:
             if k in opt:
                 raise NotImplementedError("conf key %r selects a branch outside the accelerated hot path" % k)
+        _check_img_feature(opt)
         if "ES_ocr" in opt and opt.get("ES_using_way") == "post_process":
             raise NotImplementedError("ES_using_way post_process is outside the accelerated hot path")
         if opt.get("multi2one_bidir"):
@@ -269,6 +297,10 @@ class SDNet(nn.Module):
                 pos_out = ctx_final + opt["position_dim"]
         self.ques_merger = LinearSelfAttn(q_final)
         ocr_final = {"cat": ctx_final + pos_out, "atted": pos_out, "original": ctx_final}[opt["pos_att_merge_mod"]]
+        self.img_form = img_feature_form(opt)
+        if self.img_form is not None:                   # SDNet.py:221-226, created between ques_merger and get_answer as there
+            self.img_fea_num, self.img_fea_dim, self.img_spa_dim = int(opt["img_fea_num"]), int(opt["img_fea_dim"]), int(opt["img_spa_dim"])
+            self.img_fea2od = nn.Linear(self.img_fea_dim, m2o)
         self.get_answer = GetFinalScores(ocr_final, q_final, yesno="label_yesno" in opt, no_answer="label_no_answer" in opt, useES="useES" in opt)
 
     # ------------------------------------------------------------------------------------------------------
@@ -283,6 +315,8 @@ class SDNet(nn.Module):
             host = q_list.get("_ruart_host_index")          # built by VQA_collate(prepare_index=True) in a loader worker
             frozen = "LOCK_BERT" in self.opt and not self.opt.get("bert_frozen_dropout")
             want = (self.Bert.pack, self.Bert.weights.dtype != 0, bool(frozen and self.opt.get("bert_dedup", True) and self.Bert.pack))
+            if self.img_form == "pure":          # the encoder stream without the object group (batch.BatchIndex)
+                want += ("no_od_group",)
             if host is not None and getattr(host, "plan", None) == want:
                 bi = host.to(self.device)
             else:
@@ -382,9 +416,11 @@ class SDNet(nn.Module):
         att = self.pre_align(x1, q_raw, q_mask)
         return att.reshape(-1, att.shape[2]).index_select(0, flat)
 
-    def _multi2one_last(self, x_words, idx):
+    def _multi2one_last(self, x_words, idx, under=None):
         """``multi2one`` (uni-directional LSTM, SDNet.py:137, 269-271) over real words only, returning the state at
-        each item's last word already scattered to (B, max_num, hidden) - what SDNet.py:288-318 builds item by item."""
+        each item's last word already scattered to (B, max_num, hidden) - what SDNet.py:288-318 builds item by item.
+        ``under`` (B * img_fea_num, hidden): the projected image features the object items' states are written over (the overlay
+        form, SDNet.py:280, 301-306) instead of zeros, at rows b * img_fea_num + k."""
         d = idx.dev
         rnn = self.multi2one.rnns[0]
         if L.dropout_p > 0:
@@ -394,7 +430,9 @@ class SDNet(nn.Module):
         steps = torch.split(xproj.index_select(0, d["step_rows"]), idx.n_active)      # unique rows: no sort in backward
         h0 = x_words.new_zeros(idx.N, Hh)
         h, _ = L.lstm_cell_steps(steps, rnn.weight_hh_l0, idx.n_active, h0, h0)
-        flat = d["flat_slot"]                                               # (distinct rows: a plain row scatter, see _prealign)
+        if under is not None:
+            return under.index_copy(0, d["flat_img"], h).view(idx.B, -1, Hh)
+        flat = d["flat_slot"]                                              # (distinct rows: a plain row scatter, see _prealign)
         return x_words.new_zeros(idx.B * idx.max_num, Hh).index_copy(0, flat, h).view(idx.B, idx.max_num, Hh)
 
     # ------------------------------------------------------------------------------------------------------
@@ -460,24 +498,37 @@ class SDNet(nn.Module):
             ln = getattr(layers, "_ln", None) or (None, None, None)      # a LayerNorm-folded encoder pass: the kernel normalises what it reads
             return _PoolMix.apply(lw, layers, s_, l_, dst, rows, hip.dtype_code(layers), s_last, *ln)
 
-        def front(items, idx, mix):
+        def front(items, idx, mix, under=None):
             words, raw = self._embed_items(items, idx, mix)
             if "PRE_ALIGN_befor_rnn" in opt:
                 words = torch.cat([words, self._prealign(raw, idx, q_raw, q_mask)], -1)
-            return self._multi2one_last(words, idx)                             # (B, max_num, 300)
+            return self._multi2one_last(words, idx, under)                      # (B, max_num, 300)
 
-        _fork(main, (s_q, s_od), [lw, layers, q_mask] + ([mixed] if trainable else []))
+        img_fea = None
+        if self.img_form is not None:                                           # SDNet.py:276-281
+            img_fea = q_list["img_features"].to(dev)
+            if tuple(img_fea.shape) != (Bq, self.img_fea_num, self.img_fea_dim):
+                raise ValueError("img_features %s, the conf says (%d, %d, %d)" % (tuple(img_fea.shape), Bq, self.img_fea_num, self.img_fea_dim))
+
+        _fork(main, (s_q, s_od), [lw, layers, q_mask, img_fea] + ([mixed] if trainable else []))
         with torch.cuda.stream(s_q):
             q_input, q_raw = self._embed_question(q_list, pooled(0).view(Bq, Q, H))
             ev_q = s_q.record_event() if use_streams else None
         if "PRE_ALIGN_befor_rnn" in opt:
             q_list[opt["q_emb_initial"] + "_emb"] = q_raw                      # the reference's side effect (SDNet.py:449-459)
         with torch.cuda.stream(s_od):
-            mix_od = pooled(2)
-            if ev_q is not None:
-                s_od.wait_event(ev_q)
-                _record(q_raw, s_od)
-            x_od = front(od_list, bi.od, mix_od)
+            under = None
+            if img_fea is not None:
+                # the projection is an ordinary trunk product (split-bf16, K = img_fea_dim); its input needs no gradient
+                under = ops.linear(img_fea.reshape(Bq * self.img_fea_num, self.img_fea_dim), self.img_fea2od.weight, self.img_fea2od.bias)
+            if bi.od is None:                                                   # pure form: the object items contribute nothing
+                x_od = under.view(Bq, self.img_fea_num, -1)
+            else:
+                mix_od = pooled(2)
+                if ev_q is not None:
+                    s_od.wait_event(ev_q)
+                    _record(q_raw, s_od)
+                x_od = front(od_list, bi.od, mix_od, under)
         mix_ocr = pooled(1)
         if ev_q is not None:
             main.wait_event(ev_q)
@@ -488,6 +539,8 @@ class SDNet(nn.Module):
         # ---- trunk: fixed-shape part (B, L, D) - eager, or one hipGraph replay per direction ------------------
         if "position_dim" in opt:
             ocr_pos, od_pos = ocr_list["position"].to(dev), od_list["position"].to(dev)
+            if self.img_form is not None:                                       # SDNet.py:396-397: the image boxes are the positions
+                od_pos = q_list["img_spatials"].to(dev)
         else:
             ocr_pos = od_pos = q_mask.new_zeros(1)
         trunk = self._trunk_callable(q_input, q_raw, q_mask, x_ocr, x_od, ocr_mask, od_mask, ocr_pos, od_pos)

@@ -183,6 +183,9 @@ def sdnet_param_shapes(opt):
         s["ES_linear.weight"] = (xs, d["m2o"])
         s["ES_linear.bias"] = (xs,)
         attn("ES_ocr_att", xs, d["h"], True)
+    if "img_feature" in opt:                     # Models/SDNet.py:226; after every earlier entry once more
+        s["img_fea2od.weight"] = (d["m2o"], int(opt["img_fea_dim"]))
+        s["img_fea2od.bias"] = (d["m2o"],)
     return s
 
 
@@ -256,6 +259,46 @@ def phoc_vocab_words(V, seed=1033):
     g = np.random.default_rng(seed + 41)
     alpha = "abcdefghijklmnopqrstuvwxyz0123456789"
     return ["" if i < 5 else "".join(alpha[int(k)] for k in g.integers(0, 36, size=int(g.integers(1, 13)))) for i in range(V)]
+
+
+def synthetic_image_features(opt, B, seed=3):
+    """(img_features (B, img_fea_num, img_fea_dim), img_spatials (B, img_fea_num, img_spa_dim)) float32 for a batch's question dict:
+    features |N(0, 1)| - non-negative like the pooled post-ReLU activations of a detector -, box coordinates U[0, 1).  A CPU
+    torch generator, so that every box draws the same values."""
+    g = torch.Generator().manual_seed(int(seed))
+    fea = torch.randn(B, int(opt["img_fea_num"]), int(opt["img_fea_dim"]), generator=g).abs_()
+    spa = torch.rand(B, int(opt["img_fea_num"]), int(opt["img_spa_dim"]), generator=g)
+    return fea, spa
+
+
+def synthetic_objects(opt, counts, seed=7, bert_vocab=30522):
+    """The object group of ``synthetic_batch`` with exactly ``counts`` items per sample (the ``<OD>`` sentinel included, counts[0] the
+    largest): of the ragged batches of seeds ``seed``, ``seed + 1``, ... the first whose draw gives these counts.
+    Returns (od_list, the seed it came from)."""
+    counts = [int(c) for c in counts]
+    lo = min(opt["max_ocr_num"], opt.get("ES_ocr_len", 0) + 2)
+    for s in range(seed, seed + 4096):
+        od = synthetic_batch(opt, len(counts), seed=s, n_q=2, n_ocr=lo, n_od=counts[0], bert_vocab=bert_vocab, ragged=True, targets=False)[2]
+        if od["num_cnt"] == counts:
+            return od, s
+    raise ValueError("no ragged draw with object counts %s" % (counts,))
+
+
+def synthetic_region_records(seed=3, n=3, n_box=36, dim=2048):
+    """``n`` per-image region records as a bottom-up detector's export holds them: {'path', 'features' (n_box, dim) float32, 'bbox'
+    (n_box, 4) pixel boxes x0 y0 x1 y1 - float32 for even records, float64 for odd ones -, 'image_width', 'image_height' (odd
+    numbers)}.  The features take four values (0, 0.5, 1, 1.5), so that a fixture holding them compresses; the paths carry dots in
+    their folder and stem (dataset.VQA_Dataset.get_image_feature joins the parts without them)."""
+    g = np.random.default_rng(seed)
+    recs = []
+    for i in range(n):
+        w, h = 2 * int(g.integers(200, 600)) + 1, 2 * int(g.integers(150, 400)) + 1
+        x = np.sort(g.uniform(0, w, size=(n_box, 2)), axis=1)
+        y = np.sort(g.uniform(0, h, size=(n_box, 2)), axis=1)
+        bbox = np.stack([x[:, 0], y[:, 0], x[:, 1], y[:, 1]], 1).astype(np.float32 if i % 2 == 0 else np.float64)
+        fea = np.minimum(np.floor(np.abs(g.standard_normal((n_box, dim))) * 2.0) / 2.0, 1.5).astype(np.float32)
+        recs.append({"path": "scene.v%d/im.%03d.jpg" % (i, i), "features": fea, "bbox": bbox, "image_width": w, "image_height": h})
+    return recs
 
 
 def synthetic_batch(opt, B, seed=7, n_q=30, n_ocr=100, n_od=None, bert_vocab=30522,

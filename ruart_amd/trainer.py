@@ -252,6 +252,10 @@ class SDNetTrainer(BaseTrainer):
         self.grad_sync = None
         self.global_batch = False          # opt['dp_global_batch'] in effect (setup_model)
         self.fixed_answers_len = 0
+        # conf key img_feature: a ready region-feature table {'img_id2idx', 'img_features', 'img_spatials'} for every VQA_Dataset this
+        # trainer builds (the reference fills it from hdf5, Models/SDNetTrainer.py load_image_features - not rebuilt here: set the
+        # attribute); None: the datasets read per-image files under opt['img_fea_folder']
+        self.img_features = None
         self.updates = 0
         self.best_ANLS = self.best_ACC = -1
         self.best_ANLS_batch = self.best_ACC_batch = -1
@@ -720,14 +724,14 @@ class SDNetTrainer(BaseTrainer):
             if "RESUME" in self.opt:
                 self.load_model(os.path.join(self.opt["datadir"], self.opt["MODEL_PATH"]))
             batch_st = self.opt.get("batch_st", 0)
-            train_data = VQA_Dataset(self._records("train"), self.opt)
+            train_data = VQA_Dataset(self._records("train"), self.opt, image_features=self.img_features)
             dist = torch.distributed
             rank, world = (dist.get_rank(self.process_group), dist.get_world_size(self.process_group)) \
                 if dist.is_available() and dist.is_initialized() else (0, 1)
             sampler = VQA_Sampler(train_data, self.opt["max_batch_num"], self.batch_size, True, batch_st=batch_st,
                                   epoch=self.opt.get("epoch"), rank=rank, world_size=world)
             train_loader = self._loader(train_data, sampler, workers=self.opt.get("num_worker", 0))
-            val_loader = VQA_Dataset(self._records("val"), self.opt)
+            val_loader = VQA_Dataset(self._records("val"), self.opt, image_features=self.img_features)
         it = iter(train_loader)
         # Everything alive at this point - the model, the optimizer state, the dataset records with the reference's nested python lists -
         # stays alive for the whole run: move it out of the garbage collector's sight (a permanent generation), or every full collection
@@ -780,7 +784,7 @@ class SDNetTrainer(BaseTrainer):
         self.getSaveFolder()
         self._setup_from_meta()
         self.load_model(os.path.join(self.opt["datadir"], self.opt["MODEL_PATH"]))
-        test_data = VQA_Dataset(self._records("test"), self.opt, mode="test")
+        test_data = VQA_Dataset(self._records("test"), self.opt, mode="test", image_features=self.img_features)
         return self.evaluate(test_data, 0, "test")          # a stand-alone evaluate(): closes the run-ahead stream on exit
 
     # -- checkpoints ------------------------------------------------------------------------------------------
