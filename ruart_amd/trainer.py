@@ -5,7 +5,9 @@ Kept from the reference: ``setup_model(vocab_embedding)``, ``update(batch, batch
 ``evaluate(data_loader, ...)``, ``ToCUDA(batch)``, ``load_model(path)``, ``save_for_predict(path)``,
 ``instance_bce_with_logits`` (the probabilities are fed to BCE-with-logits and scaled by the label width, :510-518),
 optimizer selection by ``opt['optimizer']`` (:307-317), global-norm clipping (:366), re-pinning of embedding rows
->= ``tune_partial`` after every step (:369-373), checkpoint format (:492-509, 453-466).
+>= ``tune_partial`` after every step (:369-373), checkpoint format (:492-509, 453-466), ``save(filename, epoch, prev_filename)``
+(:468-490) - extended to the whole run state, with ``load_state`` as its inverse and opt['save_every'] / opt['resume_state'] in
+``train()``: a resumed run is the uninterrupted run bit for bit (train_state.py).
 
 New: ``world_size > 1`` => one process per GPU, gradients averaged with RCCL (dp.GradSync) before clipping; every rank
 holds identical parameters, so the step is "N independent B-sample reference steps with averaged gradients"
@@ -257,6 +259,7 @@ class SDNetTrainer(BaseTrainer):
         # attribute); None: the datasets read per-image files under opt['img_fea_folder']
         self.img_features = None
         self.updates = 0
+        self.next_batch_i = 0              # index of the batch the next update() is due (save / load_state)
         self.best_ANLS = self.best_ACC = -1
         self.best_ANLS_batch = self.best_ACC_batch = -1
 
@@ -494,6 +497,7 @@ class SDNetTrainer(BaseTrainer):
             torch.nn.utils.clip_grad_norm_(self.network.parameters(), self.opt["grad_clipping"])
             self.optimizer.step()
         self.updates += 1
+        self.next_batch_i = batch_i + 1
         if "TUNE_PARTIAL" in self.opt:
             # Models/SDNetTrainer.py:369-373 re-pins the rows >= tune_partial after every step.  The fused optimizer never writes them
             # (FusedAdamax(pinned=): their update is left out), so they still hold the pinned values: the two 23 MB copies per step
@@ -715,15 +719,33 @@ class SDNetTrainer(BaseTrainer):
     def _train(self, train_loader, val_loader, eval_every, log_every):
         train_data = None
         batch_st = 0
+        # opt['save_every'] = N: the run state (save) after every N-th update; opt['resume_state'] = path: continue the run that file
+        # was written by.  Both absent by default: the loop below is then the loop it always was.
+        save_every = int(self.opt.get("save_every") or 0)
+        resume = self.opt.get("resume_state")
+        state = None
+        if save_every < 0:
+            raise ValueError("opt['save_every'] = %r: a positive number of updates" % (self.opt.get("save_every"),))
+        if save_every or resume:
+            self._refuse_state_conf("opt['save_every'] / opt['resume_state']")
+        if resume:
+            from . import train_state as TS
+            state = TS.read(resume)
+            batch_st = int(state["ruart"]["next_batch"])
+            if "batch_st" in self.opt and int(self.opt["batch_st"]) != batch_st:
+                raise ValueError("opt['batch_st'] = %r, the run state %s continues at batch %d" % (self.opt["batch_st"], resume, batch_st))
+            # the run goes on where it was: no new run_<n>, conf_copy left alone
+            self.saveFolder = os.path.dirname(os.path.abspath(resume))
         if train_loader is None:
             from .dataset import VQA_Dataset
-            if self._is_main():
+            if self._is_main() and not resume:
                 self.getSaveFolder()
                 self.saveConf()
             self._setup_from_meta()
             if "RESUME" in self.opt:
                 self.load_model(os.path.join(self.opt["datadir"], self.opt["MODEL_PATH"]))
-            batch_st = self.opt.get("batch_st", 0)
+            if not resume:
+                batch_st = self.opt.get("batch_st", 0)
             train_data = VQA_Dataset(self._records("train"), self.opt, image_features=self.img_features)
             dist = torch.distributed
             rank, world = (dist.get_rank(self.process_group), dist.get_world_size(self.process_group)) \
@@ -755,6 +777,11 @@ class SDNetTrainer(BaseTrainer):
             batch, nxt = stage(), None
             if batch is not None:
                 nxt = stage()                                             # one batch of lookahead feeds the BERT prefetch
+            if state is not None:
+                # applied HERE: the loader's iterator drew its seed from torch's CPU generator and the sampler reseeded numpy on its
+                # way to the two staged batches - in the uninterrupted run both lay before the save, so the streams go in after them
+                self._apply_state(state)
+                state = None
             batch_i = batch_st
             while batch is not None:
                 if val_loader is not None and batch_i % eval_every == 0:
@@ -768,6 +795,10 @@ class SDNetTrainer(BaseTrainer):
                     cur = float(loss)
                     log.info("updates[%6d] train loss[%8.5f / %8.5f]", self.updates, self.train_loss.avg, cur)
                 batch_i += 1
+                if save_every and batch_i % save_every == 0:
+                    # before the evaluation batch_i may start with: the resumed run repeats it, as this run goes on to do
+                    epoch = batch_i * self.batch_size * self._state_ranks()[1] // max(len(train_data), 1) if train_data is not None else None
+                    self.save(os.path.join(self.saveFolder, "train_state.pt"), epoch=epoch)
             self._in_train_loop = False
             self.flush_readback()                            # the last step's loss and asserts
             if train_data is not None:                       # :121-122
@@ -798,16 +829,109 @@ class SDNetTrainer(BaseTrainer):
             state.setdefault(k, v)
         self.network.load_state_dict(state)
 
-    def save_for_predict(self, filename):
-        """:492-509 - network weights without BERT / fixed embeddings, plus the config."""
-        self.flush_readback()
+    def _predict_state(self):
+        """name -> tensor of what ``save_for_predict`` writes (live tensors, nothing copied)."""
         full = self.network.state_dict()
         # (of the encoder, only tensors its passes use: the checkpoint's pooler head is a parameter too and never gets a gradient)
         used = set("Bert.bert_model." + n for n in getattr(getattr(getattr(self.network, "Bert", None), "bert_model", None), "_order", ()))
         trained = [n for n, p in self.network.named_parameters() if p.requires_grad and (not n.startswith("Bert.bert_model.") or n in used)]
-        state = {k: full[k] for k in predict_checkpoint_keys(full, self.opt, trained)}
+        return {k: full[k] for k in predict_checkpoint_keys(full, self.opt, trained)}
+
+    def save_for_predict(self, filename):
+        """:492-509 - network weights without BERT / fixed embeddings, plus the config."""
+        self.flush_readback()
+        state = self._predict_state()
         cfg = {k: v for k, v in self.opt.items() if isinstance(v, (int, float, str, bool))}
         try:
             torch.save({"state_dict": {"network": state}, "config": cfg}, filename)
         except BaseException:
             log.info("[ WARN: Saving failed... continuing anyway. ]")
+
+    # -- run state: resume a run exactly (train_state.py) --------------------------------------------------------------
+    def _refuse_state_conf(self, what):
+        """Confs whose resumed run was never established to be the uninterrupted run are refused, not served inexactly."""
+        if self.opt.get("ruart_graph_trunk", False):
+            raise ValueError("%s does not combine with opt['ruart_graph_trunk']: the captured trunk draws its dropout masks inside a "
+                             "replayed graph, and an exact resume was never established there" % what)
+
+    def _state_ranks(self):
+        """(rank, world) of the run state: the data-parallel group's when this trainer exchanges gradients, else (0, 1)."""
+        if self.grad_sync is None:
+            return 0, 1
+        return torch.distributed.get_rank(self.process_group), torch.distributed.get_world_size(self.process_group)
+
+    def _banks(self):
+        """The two mask banks a step draws from: the module-level one (embedding and multi2one masks) and the trunk's own."""
+        return {"front": L.mask_bank, "trunk": self.network._trunk_module()._bank}
+
+    def _trainable_names(self):
+        return [n for n, p in self.network.named_parameters() if p.requires_grad]
+
+    def _pack_state(self, epoch, ranks):
+        from . import train_state as TS
+        full = self.network.state_dict()
+        state = self._predict_state()
+        trainable = self._trainable_names()
+        for n in trainable:                  # a trained encoder's tensors included; a frozen encoder comes from BERT_model_file again
+            state.setdefault(n, full[n])
+        best = {"ANLS": self.best_ANLS, "ACC": self.best_ACC, "ANLS_batch": self.best_ANLS_batch, "ACC_batch": self.best_ACC_batch}
+        return TS.pack(state, self.optimizer, self.updates, self.train_loss, self.opt, epoch=epoch, trainable=trainable,
+                       next_batch=self.next_batch_i, best=best, ranks=ranks, extra={"rank_seeded": bool(self._rank_seeded)})
+
+    def save(self, filename, epoch=None, prev_filename=None):
+        """Models/SDNetTrainer.py:468-490, extended to the whole run state (train_state.py): network (what ``save_for_predict`` writes
+        plus every trained tensor), optimizer, ``updates``, ``train_loss``, ``epoch`` - and the best-model records, the index of the
+        next batch, every rank's random streams and mask banks.  ``load_model`` reads the file as a weights-only checkpoint,
+        ``load_state`` continues the run bit for bit.  With data parallelism a COLLECTIVE call: every rank contributes its streams and
+        banks, rank 0 writes.  The file appears under its name whole or not at all (temporary name + rename); a failed write is
+        logged and training goes on, as in ``save_for_predict``."""
+        from . import train_state as TS
+        self._refuse_state_conf("SDNetTrainer.save")
+        self.flush_readback()                  # the deferred asserts come before any weight is written
+        rank, world = self._state_ranks()
+        ranks = TS.gather_ranks(TS.capture_rank(self.device, self._banks()), world, self.process_group)
+        if rank != 0:
+            return
+        # read on the step stream: ordered behind the optimizer's raw-pointer writes without a device-wide synchronise
+        ckpt = self.on_step_stream(self._pack_state, epoch, ranks)
+        try:
+            TS.write(ckpt, filename)
+            log.info("run state saved to %s", filename)
+            if prev_filename and os.path.abspath(prev_filename) != os.path.abspath(filename) and os.path.exists(prev_filename):
+                os.remove(prev_filename)
+        except Exception:
+            log.info("[ WARN: Saving failed... continuing anyway. ]")
+
+    def load_state(self, filename):
+        """Continue the run ``save`` wrote: returns the index of the next batch.  After ``setup_model`` (and after ``load_model``, if
+        both are wanted).  Everything is copied in place - the fused optimizers' pointer tables stay valid - and each data-parallel
+        rank takes its own random streams and mask banks.  ValueError, naming the mismatch, for a state that does not fit this run:
+        optimizer class or rule, a missing or mis-shaped trainable tensor, the world size, the format version."""
+        from . import train_state as TS
+        if not hasattr(self, "network"):
+            raise RuntimeError("load_state needs setup_model() done")
+        self._refuse_state_conf("SDNetTrainer.load_state")
+        return self._apply_state(TS.read(filename))
+
+    def _apply_state(self, ckpt):
+        from . import train_state as TS
+        rank, world = self._state_ranks()
+        named = dict(self.network.named_buffers())
+        named.update(self.network.named_parameters())
+        TS.check(ckpt, self.optimizer, named, self._trainable_names(), world)
+        self.flush_readback()
+
+        def copy_in():
+            TS.restore_tensors(ckpt, named)
+            self.optimizer.load_state_dict(ckpt["state_dict"]["optimizer"])
+
+        self.on_step_stream(copy_in)
+        ruart = ckpt["ruart"]
+        self.updates = int(ckpt["state_dict"]["updates"])
+        TS.restore_meter(self.train_loss, ckpt["train_loss"])
+        b = ruart["best"]
+        self.best_ANLS, self.best_ACC, self.best_ANLS_batch, self.best_ACC_batch = b["ANLS"], b["ACC"], b["ANLS_batch"], b["ACC_batch"]
+        self._rank_seeded = bool(ruart.get("rank_seeded", self._rank_seeded))
+        self.next_batch_i = int(ruart["next_batch"])
+        TS.restore_rank(ruart["ranks"][rank], self.device, self._banks())       # last: nothing above may draw from a stream
+        return self.next_batch_i
