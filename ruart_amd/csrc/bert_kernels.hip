@@ -60,7 +60,40 @@ __device__ __forceinline__ void ln_row_finish(f32x4_t (&v)[MAXG], int H, int lan
       }
     }
   }
-  const float var = wave_sum(q) / (float)H;
+  float var = wave_sum(q) / (float)H;
+  // A row far from zero (|mean| > its standard deviation; uniform over the wave): the fp32 row sum is good to ~2^-24 of the SUM, and
+  // the mean sits on fp32's grid at |mean|, so every centred value is off by up to an ulp of the mean - at mean 30, std 1 several f16
+  // ulps of the outputs near zero.  The centred values are (nearly) exact differences, so their sum recovers what was lost; it stays a
+  // separate low part of the mean (mean + mlo would round back onto the same grid), and the second moment is taken again.  Rows whose
+  // sums are exact (constant rows) get mlo == 0.  Every other row keeps the plain two-pass arithmetic above, bit for bit.
+  // Why a guard and not every row: the compensation moves the last bits of every LayerNorm output of the encoder, and with it on
+  // unconditionally tests/test_gpu_dp_global_batch.py (two ranks against one B = 8 step) saw one trunk gradient at 1.08e-4 of its 1e-4
+  // bound.  Hidden rows of a real encoder have |mean| well below their std and almost never take this branch: it serves rows with a
+  // large offset (tests/test_gpu_encoder_kernels.py), at the price of a discontinuity of ~2^-24 |mean| / std at the threshold, where
+  // a row just under it keeps the plain mean.
+  float mlo = 0.f;
+  if (mean * mean > var) {
+    float e = 0.f;
+#pragma unroll
+    for (int i = 0; i < MAXG; ++i) {
+      const int c = (i * 64 + lane) * 4;
+      if (c < H) e += ((v[i][0] - mean) + (v[i][1] - mean)) + ((v[i][2] - mean) + (v[i][3] - mean));
+    }
+    mlo = wave_sum(e) / (float)H;
+    q = 0.f;
+#pragma unroll
+    for (int i = 0; i < MAXG; ++i) {
+      const int c = (i * 64 + lane) * 4;
+      if (c < H) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float d = (v[i][r] - mean) - mlo;
+          q += d * d;
+        }
+      }
+    }
+    var = wave_sum(q) / (float)H;
+  }
   const float rstd = 1.0f / sqrtf(var + eps);
 #pragma unroll
   for (int i = 0; i < MAXG; ++i) {
@@ -69,7 +102,7 @@ __device__ __forceinline__ void ln_row_finish(f32x4_t (&v)[MAXG], int H, int lan
       const f32x4_t g = load4(gamma + c), b = load4(beta + c);
       f32x4_t o;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) o[r] = g[r] * ((v[i][r] - mean) * rstd) + b[r];
+      for (int r = 0; r < 4; ++r) o[r] = g[r] * (((v[i][r] - mean) - mlo) * rstd) + b[r];
       out(c, o);
     }
   }
