@@ -99,6 +99,14 @@ class _FusedAttention(torch.autograd.Function):
         gout = gout.contiguous()
         ga, gk, gv = torch.empty_like(pa), torch.empty_like(pk), torch.empty_like(v)
         ds = torch.empty_like(probs)
+        kdiag = diag
+        if dl == 1 and ctx.needs_input_grad[4]:
+            # a trainable scalar diag (the model's own is frozen): the kernels return grad_diag partials per column for a vector diag
+            # only, so the backward runs with the scalar spread over the h columns - the same products, hence the same bits in every other
+            # gradient - and the scalar's gradient is the sum of the column gradients
+            if h == 1:
+                raise hip.HipError("fused_attention: no gradient for a scalar diag with h == 1 (a one-column diag is the scalar form)")
+            kdiag, dl = diag.reshape(1).expand(h).contiguous(), h
         gdiag = (torch.empty(B * ((L1 + 15) // 16), h, dtype=torch.float32, device=pa.device)
                  if (dl > 1 and ctx.needs_input_grad[4]) else None)
         if "attn" in _ABL_SKIP:
@@ -106,9 +114,12 @@ class _FusedAttention(torch.autograd.Function):
                 if t is not None:
                     t.zero_()
         else:
-            lib.ruart_attn_bwd_pscale(pa, pk, v, probs, gout, diag, dl, ctx.relu, pscale, ga, gk, gv, gdiag, ds, B, L1, L2, h, D3,
+            lib.ruart_attn_bwd_pscale(pa, pk, v, probs, gout, kdiag, dl, ctx.relu, pscale, ga, gk, gv, gdiag, ds, B, L1, L2, h, D3,
                                       hip.stream_ptr())
-        return ga, gk, gv, None, (colsum(gdiag).view_as(diag) if gdiag is not None else None), None, None
+        if gdiag is None:
+            return ga, gk, gv, None, None, None, None
+        gd = colsum(gdiag)
+        return ga, gk, gv, None, (gd if kdiag is diag else gd.sum()).view_as(diag), None, None
 
 
 def fused_attention(a, k, v, mask, diag=None, relu=False, prob_scale=None):
