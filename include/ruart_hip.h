@@ -473,7 +473,7 @@ int ruart_scorer_heads_bwd(const float* x, const float* u1, const float* u2, con
  *   cells : (B, T, ndir*h)   c_t                       }
  *   hprev : (B, T, ndir*h)   h of the previous step of the same direction (0 at its first step): the right-hand operand of
  *                            grad_W_hh = grad_xproj^T . hprev, so the caller needs no shifted copy of y
- * h <= 128, ndir in {1, 2}. */
+ * h <= 128, ndir in {1, 2} (hipErrorInvalidValue otherwise; 128 < h <= 256: ruart_lstm_wide_fwd / _bwd below). */
 /* Kernel form of ruart_lstm_fwd / ruart_lstm_bwd: 1 (default) = 16 batch rows per workgroup, the recurrent product on the matrix cores
  * with split-bf16 operands (hi.hi + hi.lo + lo.hi, fp32 accumulation - the arithmetic of ruart_gemm_x3), B * ndir / 16 workgroups;
  * 0 = one workgroup per (row, direction) with exact fp32 FMAs (rounds 1-2).  Process-wide. */
@@ -485,6 +485,18 @@ int ruart_lstm_fwd(const float* xproj, const float* w_hh, float* y, float* gates
  * by the caller. */
 int ruart_lstm_bwd(const float* grad_y, const float* w_hh, const float* gates, const float* cells, float* grad_xproj, int B,
                    int T, int h, int ndir, void* stream);
+
+/* The same recurrence and BPTT for 128 < h <= 256, same tensors, arithmetic and NaN flag: W_hh does not fit a CU's registers there, so each
+ * call first writes it - split into bf16 hi / lo, in MFMA fragment order - into the caller's workspace `ws` (>= ruart_lstm_wide_ws_bytes,
+ * 16-byte aligned) and the persistent kernel streams that image from L2 every step.  Each of the two calls prepares its own image (they may
+ * be given different workspaces); `ws` must stay untouched until the call's kernels have run.  No allocation, no sync.
+ * hipErrorInvalidValue - before anything is launched - for h <= 128, h > 256, ndir outside {1, 2}, B <= 0, T <= 0, a NULL ws or
+ * ws_bytes too small.  ws_bytes(with_backward = 1) serves either call. */
+int ruart_lstm_wide_ws_bytes(int h, int ndir, int with_backward, size_t* bytes);
+int ruart_lstm_wide_fwd(const float* xproj, const float* w_hh, float* y, float* gates, float* cells, float* hprev, int B, int T, int h,
+                        int ndir, void* ws, size_t ws_bytes, void* stream);
+int ruart_lstm_wide_bwd(const float* grad_y, const float* w_hh, const float* gates, const float* cells, float* grad_xproj, int B,
+                        int T, int h, int ndir, void* ws, size_t ws_bytes, void* stream);
 
 /* The operands of one BIDIRECTIONAL nn.LSTM layer (Models/Layers.py:124-180 via nn.LSTM; torch's parameter layout, G = 4h gate rows) in
  * one launch: w (2G, K) = [w_ih ; w_ih_reverse] for the input projection of both directions, b (2G) = [b_ih + b_hh ; the reverse pair],

@@ -458,6 +458,340 @@ __global__ __launch_bounds__(512) void lstm_bwd_mfma_kernel(const float* __restr
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// The same recurrence for 128 < h <= 256 (ruart_lstm_wide_fwd / _bwd): the weights are STREAMED.
+//
+// At h = 256 the bf16 hi / lo image of one direction's W_hh is 4 . 256 . 256 . 4 B = 1 MiB: neither a CU's registers (512 KiB) nor its
+// LDS (160 KiB) hold it.  Everything else is lstm_fwd_mfma_kernel's: one workgroup owns 16 batch rows of one direction for the whole
+// sequence, lane (fr, fq) of a wave owns all four gates of four consecutive units of batch row fr, the cell update is lane-local, the new
+// h goes into the double-buffered bf16 hi / lo LDS image.  There are 256 ownership positions now, in 16 groups of 16: wave w owns groups
+// 2 w and 2 w + 1 (lstm_unit / lstm_counted with the group index where the narrow kernels have the wave index).  A preparation kernel
+// writes W_hh once per launch, split and already in MFMA fragment order, into the caller's workspace; every step each wave reads ITS slice
+// of that image back from L2 with 16-byte loads, 1 KiB per wave instruction, one (k-step, group) chunk - 4 gates x hi / lo = 8 loads -
+// ahead of the MFMAs that use it.  The stream does not depend on the step, so the prefetch runs across the step boundary (the last chunk
+// of a step prefetches the first chunk of the next).  k-steps past ceil(h / 32), groups past ceil(h / 16) and waves that own no live group
+// are skipped with wave-uniform branches: h = 144 streams 5 k-steps, not 8.  No workgroup waits for another one.
+// Arithmetic: per k-step lo.hi, hi.lo, then hi.hi into one fp32 accumulator per gate (the resident kernel runs all small terms of a step
+// before all hi.hi ones; with a streamed W that would need two passes over the image).
+// Backward: dh_{t-1} (16 x 256 positions) = da_t (16 x 1024) . W_hh.  As in lstm_bwd_mfma_kernel every wave contracts over ITS OWN
+// positions (2 groups x 4 gate types = 4 k-steps, da straight from its registers) for all live output tiles, streaming the transposed
+// image one output tile (8 loads) ahead; a tile's partial sum goes to LDS as soon as its 12 MFMAs are done and the waves' partial sums
+// meet there (128 KB, one buffer: two barriers per step).
+// Registers (hipcc -O3, gfx950, -Rpass-analysis=kernel-resource-usage): lstm_wide_fwd_kernel 214 VGPRs, lstm_wide_bwd_kernel 220 VGPRs; no
+// AGPRs, no scratch, 2 waves per SIMD (512 threads); LDS 33 KB / 128 KB.  Measured (profiles/lstm_wide.txt): forward 12.2 us per step at
+// h = 256, 6.0 us at h = 144.
+// ---------------------------------------------------------------------------------------------------------
+#define WLHS 528               // wide forward h image: 256 bf16 per row + 16 bytes pad
+#define WSLOTS_CHUNK 512       // 16-byte slots of one streamed chunk: 8 fragments x 64 lanes (8 KiB)
+
+// Forward image, in 16-byte slots: [direction][wave w < KS][k-step ks < KS][group 2 w + gl][gate i][hi | lo][lane], KS = ceil(h / 32).
+// Slot (.., lane (fr, fq)) = first MFMA operand of tile (gate row i h + unit(2 w + gl, fr), contraction positions 32 ks + 8 fq .. + 7).
+__global__ __launch_bounds__(256) void lstm_wide_prep_fwd_kernel(const float* __restrict__ w_hh, bf16x8_t* __restrict__ img, int h, int KS,
+                                                                 int total) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int lane = idx & 63, p = (idx >> 6) & 1, i = (idx >> 7) & 3, gl = (idx >> 9) & 1;
+  int r = idx >> 10;
+  const int ks = r % KS;
+  r /= KS;
+  const int w = r % KS, d = r / KS;
+  const int fr = lane & 15, fq = lane >> 4;
+  const int unit = lstm_unit(2 * w + gl, fr, h);
+  const float* row = w_hh + ((size_t)d * 4 * h + (size_t)i * h + unit) * h;
+  bf16x8_t out;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const int k = ks * 32 + fq * 8 + e;
+    const float v = lstm_counted(k, h) ? row[lstm_unit(k >> 4, k & 15, h)] : 0.f;
+    bf16_t a, b;
+    split_bf16_(v, a, b);
+    out[e] = p ? b : a;
+  }
+  img[idx] = out;
+}
+
+// Backward image: [direction][producer wave w < KS][output tile t < 2 KS][k-step j = 2 gl + jj][hi | lo][lane].  Slot = first operand of
+// (output position (t, fr) -> unit(t, fr); contraction element e of lane group fq = gate type 2 jj + (e >> 2) of position 4 fq + (e & 3) of
+// group 2 w + gl); duplicate contraction positions carry zero weights.
+__global__ __launch_bounds__(256) void lstm_wide_prep_bwd_kernel(const float* __restrict__ w_hh, bf16x8_t* __restrict__ img, int h, int KS,
+                                                                 int total) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int lane = idx & 63, p = (idx >> 6) & 1, j = (idx >> 7) & 3;
+  int r = idx >> 9;
+  const int t = r % (2 * KS);
+  r /= 2 * KS;
+  const int w = r % KS, d = r / KS;
+  const int fr = lane & 15, fq = lane >> 4;
+  const int unit = lstm_unit(t, fr, h);
+  const int g = 2 * w + (j >> 1);
+  bf16x8_t out;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const int type = 2 * (j & 1) + (e >> 2), m = 4 * fq + (e & 3);
+    const int gu = lstm_unit(g, m, h);
+    const float v = lstm_counted(16 * g + m, h) ? w_hh[((size_t)d * 4 * h + (size_t)type * h + gu) * h + unit] : 0.f;
+    bf16_t a, b;
+    split_bf16_(v, a, b);
+    out[e] = p ? b : a;
+  }
+  img[idx] = out;
+}
+
+__device__ __forceinline__ bf16x8_t bf16x8_zero_() { return __builtin_bit_cast(bf16x8_t, (f32x4_t){0.f, 0.f, 0.f, 0.f}); }
+__device__ __forceinline__ void lstm_wide_loadw(bf16x8_t (&f)[8], const bf16x8_t* p) {
+#pragma unroll
+  for (int q = 0; q < 8; ++q) f[q] = p[q * 64];
+}
+
+__global__ __launch_bounds__(512) void lstm_wide_fwd_kernel(const float* __restrict__ xproj, const bf16x8_t* __restrict__ wimg,
+                                                            float* __restrict__ y, float* __restrict__ gates, float* __restrict__ cells,
+                                                            float* __restrict__ hprev, int B, int T, int h, int ndir,
+                                                            int* __restrict__ nan_flag) {
+  __shared__ __attribute__((aligned(16))) char himg[2][2][LRB * WLHS];      // [buffer][hi | lo], k = ownership position, 33 KB
+  const int d = blockIdx.y;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, fr = lane & 15, fq = lane >> 4;
+  const int G = 4 * h, KS = (h + 31) >> 5;
+  const bool live0 = 32 * w < h, live1 = 32 * w + 16 < h;      // wave-uniform: does group 2 w / 2 w + 1 hold a real unit?
+  for (int i = tid; i < 2 * 2 * LRB * WLHS / 4; i += 512) reinterpret_cast<int*>(&himg[0][0][0])[i] = 0;     // h_0 = 0; pads and dead groups stay 0
+  const int b = min((int)blockIdx.x * LRB + fr, B - 1);
+  const int uo0 = min(32 * w + 4 * fq, h - 4), uo1 = min(32 * w + 16 + 4 * fq, h - 4);      // first of the lane's four units, per group
+  float c[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}, hp[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+  const size_t ldx = (size_t)ndir * G, ldy = (size_t)ndir * h;
+  const int t0 = d ? T - 1 : 0, dt = d ? -1 : 1;
+  const long long sx = (long long)dt * (long long)ldx, sy = (long long)dt * (long long)ldy;
+  const float* xp = xproj + ((size_t)b * T + t0) * ldx + (size_t)d * G;
+  const size_t oy = ((size_t)b * T + t0) * ldy + (size_t)d * h, og_ = ((size_t)b * T + t0) * ldx + (size_t)d * G;
+  float* yp = y + oy;
+  float* cp_ = cells ? cells + oy : nullptr;
+  float* hpp = hprev ? hprev + oy : nullptr;
+  float* gp = gates ? gates + og_ : nullptr;
+  const bf16x8_t* wp = wimg + (size_t)(d * KS + (live0 ? w : 0)) * KS * (2 * WSLOTS_CHUNK) + lane;      // this wave's slice of the image
+  auto load_x = [&](const float* p, f32x4_t (&x)[4]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const f32x4_u v = *reinterpret_cast<const f32x4_u*>(p + (size_t)i * h);
+      x[i] = (f32x4_t){v[0], v[1], v[2], v[3]};
+    }
+  };
+  // 12 MFMAs of one (k-step, group) chunk; consecutive MFMAs never touch the same accumulator
+  auto mma = [&](f32x4_t (&acc)[4], const bf16x8_t (&f)[8], bf16x8_t hh, bf16x8_t hl) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) acc[i] = mfma_16x16x32(f[2 * i + 1], hh, acc[i]);       // small terms first
+#pragma unroll
+    for (int i = 0; i < 4; ++i) acc[i] = mfma_16x16x32(f[2 * i], hl, acc[i]);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) acc[i] = mfma_16x16x32(f[2 * i], hh, acc[i]);
+  };
+  bool bad = false;
+  // lane-local cell update of the four units at offset uo (ownership positions pos .. pos + 3 of row fr), and everything it stores
+  auto cell = [&](const f32x4_t (&acc)[4], const f32x4_t (&x)[4], float (&cc)[4], float (&hq)[4], int uo, int pos, char* hi_img, char* lo_img) {
+    f32x4_t ga[4], hv, cv, hpv;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float pi = acc[0][r] + x[0][r], pf = acc[1][r] + x[1][r], pg = acc[2][r] + x[2][r], po = acc[3][r] + x[3][r];
+      const float ig = sigm_(pi), fg = sigm_(pf), gg = tanh_(pg), og = sigm_(po);
+      cc[r] = fg * cc[r] + ig * gg;
+      const float hn = og * tanh_(cc[r]);
+      ga[0][r] = ig; ga[1][r] = fg; ga[2][r] = gg; ga[3][r] = og;
+      hv[r] = hn;
+      cv[r] = cc[r];
+      hpv[r] = hq[r];
+      hq[r] = hn;
+      bad |= !(hn == hn);
+    }
+    bf16x4_t vh, vl;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      bf16_t a, bb;
+      split_bf16_(hv[r], a, bb);
+      vh[r] = a;
+      vl[r] = bb;
+    }
+    *reinterpret_cast<bf16x4_t*>(hi_img + fr * WLHS + pos * 2) = vh;
+    *reinterpret_cast<bf16x4_t*>(lo_img + fr * WLHS + pos * 2) = vl;
+    *reinterpret_cast<f32x4_u*>(yp + uo) = (f32x4_u){hv[0], hv[1], hv[2], hv[3]};
+    if (cp_) *reinterpret_cast<f32x4_u*>(cp_ + uo) = (f32x4_u){cv[0], cv[1], cv[2], cv[3]};
+    if (hpp) *reinterpret_cast<f32x4_u*>(hpp + uo) = (f32x4_u){hpv[0], hpv[1], hpv[2], hpv[3]};
+    if (gp) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) *reinterpret_cast<f32x4_u*>(gp + uo + (size_t)i * h) = (f32x4_u){ga[i][0], ga[i][1], ga[i][2], ga[i][3]};
+    }
+  };
+  f32x4_t x0[4], x1[4], xn0[4], xn1[4];
+  bf16x8_t wa[8], wb[8];
+  load_x(xp + uo0, x0);                               // (dead groups load their clamped, real units: unconditional, never used)
+  load_x(xp + uo1, x1);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    xn0[i] = x0[i];
+    xn1[i] = x1[i];
+    wb[i] = wb[i + 4] = bf16x8_zero_();
+  }
+  lstm_wide_loadw(wa, wp);                            // chunk (ks 0, group 0) of the first step
+  __syncthreads();
+  int cur = 0;
+  for (int s = 0; s < T; ++s, cur ^= 1) {
+    xp += sx;
+    if (live0) {
+      if (s + 1 < T) {
+        load_x(xp + uo0, xn0);
+        load_x(xp + uo1, xn1);
+      }
+      f32x4_t acc0[4], acc1[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) acc0[i] = acc1[i] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+      for (int ks = 0; ks < KS; ++ks) {
+        const bf16x8_t hh = *reinterpret_cast<const bf16x8_t*>(&himg[cur][0][fr * WLHS + (ks * 32 + fq * 8) * 2]);
+        const bf16x8_t hl = *reinterpret_cast<const bf16x8_t*>(&himg[cur][1][fr * WLHS + (ks * 32 + fq * 8) * 2]);
+        if (live1) lstm_wide_loadw(wb, wp + (size_t)ks * (2 * WSLOTS_CHUNK) + WSLOTS_CHUNK);
+        mma(acc0, wa, hh, hl);
+        lstm_wide_loadw(wa, wp + (size_t)(ks + 1 < KS ? ks + 1 : 0) * (2 * WSLOTS_CHUNK));      // wraps into the next step
+        if (live1) mma(acc1, wb, hh, hl);
+      }
+      cell(acc0, x0, c[0], hp[0], uo0, 32 * w + 4 * fq, &himg[cur ^ 1][0][0], &himg[cur ^ 1][1][0]);
+      if (live1) cell(acc1, x1, c[1], hp[1], uo1, 32 * w + 16 + 4 * fq, &himg[cur ^ 1][0][0], &himg[cur ^ 1][1][0]);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        x0[i] = xn0[i];
+        x1[i] = xn1[i];
+      }
+    }
+    yp += sy;
+    if (cp_) cp_ += sy;
+    if (hpp) hpp += sy;
+    if (gp) gp += sx;
+    __syncthreads();                                   // the new h image is complete; the old one is dead for every wave
+  }
+  if (bad && nan_flag) atomicOr(nan_flag, 1);
+}
+
+__global__ __launch_bounds__(512) void lstm_wide_bwd_kernel(const float* __restrict__ grad_y, const bf16x8_t* __restrict__ wimg,
+                                                            const float* __restrict__ gates, const float* __restrict__ cells,
+                                                            float* __restrict__ grad_xproj, int B, int T, int h, int ndir) {
+  __shared__ __attribute__((aligned(16))) float part[8][16][64 * 4];      // [producer wave][output tile][lane x 4], 128 KB
+  const int d = blockIdx.y;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, fr = lane & 15, fq = lane >> 4;
+  const int G = 4 * h, KS = (h + 31) >> 5, NG = (h + 15) >> 4;
+  const bool live0 = 32 * w < h, live1 = 32 * w + 16 < h;
+  const int b = min((int)blockIdx.x * LRB + fr, B - 1);
+  const int uo0 = min(32 * w + 4 * fq, h - 4), uo1 = min(32 * w + 16 + 4 * fq, h - 4);
+  const size_t ldx = (size_t)ndir * G, ldy = (size_t)ndir * h;
+  const int t0 = d ? 0 : T - 1, dt = d ? 1 : -1;       // the forward order walked backwards
+  const long long sx = (long long)dt * (long long)ldx, sy = (long long)dt * (long long)ldy;
+  float dh_rec[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}, dc_next[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+  struct StepIn { f32x4_t ig, fg, gg, og, cc, cp, gy; };
+  const float* gp = gates + ((size_t)b * T + t0) * ldx + (size_t)d * G;
+  const float* cp_ = cells + ((size_t)b * T + t0) * ldy + (size_t)d * h;
+  const float* gyp = grad_y + ((size_t)b * T + t0) * ldy + (size_t)d * h;
+  float* gx = grad_xproj + ((size_t)b * T + t0) * ldx + (size_t)d * G;
+  const bf16x8_t* wp = wimg + (size_t)(d * KS + (live0 ? w : 0)) * (2 * KS) * WSLOTS_CHUNK + lane;      // this wave's slice: 2 KS tile chunks
+  auto ld = [&](const float* p) -> f32x4_t {
+    const f32x4_u v = *reinterpret_cast<const f32x4_u*>(p);
+    return (f32x4_t){v[0], v[1], v[2], v[3]};
+  };
+  auto load_step = [&](bool prev, int uo, StepIn& in) {
+    in.ig = ld(gp + uo);
+    in.fg = ld(gp + uo + h);
+    in.gg = ld(gp + uo + 2 * (size_t)h);
+    in.og = ld(gp + uo + 3 * (size_t)h);
+    in.cc = ld(cp_ + uo);
+    in.cp = ld(prev ? cp_ + uo + sy : cp_ + uo);       // (multiplied by 0 below when there is none)
+    in.gy = ld(gyp + uo);
+  };
+  // da_i..da_o of the lane's four units of one group -> global grad_xproj and the second MFMA operands of its two k-steps (hi, lo)
+  auto step_da = [&](const StepIn& in, float (&dhr)[4], float (&dcn)[4], float has_prev, int uo, bf16x8_t* fh, bf16x8_t* fl) {
+    f32x4_t da[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float dh = in.gy[r] + dhr[r];
+      const float tc = tanh_(in.cc[r]);
+      const float dc = dcn[r] + dh * in.og[r] * (1.f - tc * tc);
+      da[0][r] = dc * in.gg[r] * in.ig[r] * (1.f - in.ig[r]);
+      da[1][r] = dc * (in.cp[r] * has_prev) * in.fg[r] * (1.f - in.fg[r]);
+      da[2][r] = dc * in.ig[r] * (1.f - in.gg[r] * in.gg[r]);
+      da[3][r] = dh * tc * in.og[r] * (1.f - in.og[r]);
+      dcn[r] = dc * in.fg[r];
+    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        bf16_t a, bb;
+        split_bf16_(da[2 * j + (e >> 2)][e & 3], a, bb);
+        fh[j][e] = a;
+        fl[j][e] = bb;
+      }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) *reinterpret_cast<f32x4_u*>(gx + uo + (size_t)i * h) = (f32x4_u){da[i][0], da[i][1], da[i][2], da[i][3]};
+  };
+  // one output tile: 4 k-steps x 3 products into four independent accumulators, combined in a fixed order
+  auto tile = [&](const bf16x8_t (&f)[8], const bf16x8_t (&fh)[4], const bf16x8_t (&fl)[4], float* out) {
+    f32x4_t a[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) a[j] = mfma_16x16x32(f[2 * j + 1], fh[j], (f32x4_t){0.f, 0.f, 0.f, 0.f});       // small terms first
+#pragma unroll
+    for (int j = 0; j < 4; ++j) a[j] = mfma_16x16x32(f[2 * j], fl[j], a[j]);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) a[j] = mfma_16x16x32(f[2 * j], fh[j], a[j]);
+    *reinterpret_cast<f32x4_t*>(out) = (a[0] + a[1]) + (a[2] + a[3]);
+  };
+  StepIn in0, in1, n0, n1;
+  load_step(T > 1, uo0, in0);
+  load_step(T > 1, uo1, in1);
+  n0 = in0;
+  n1 = in1;
+  bf16x8_t wa[8], wb[8];
+#pragma unroll
+  for (int q = 0; q < 8; ++q) wb[q] = bf16x8_zero_();
+  lstm_wide_loadw(wa, wp);                            // output tile 0 of the first step
+  for (int s = 0; s < T; ++s) {
+    if (live0) {
+      const float has_prev = (s + 1 < T) ? 1.f : 0.f;
+      bf16x8_t fh[4], fl[4];
+      step_da(in0, dh_rec[0], dc_next[0], has_prev, uo0, fh, fl);
+      if (live1) {
+        step_da(in1, dh_rec[1], dc_next[1], has_prev, uo1, fh + 2, fl + 2);
+      } else {
+        fh[2] = fh[3] = fl[2] = fl[3] = bf16x8_zero_();
+      }
+      gp += sx;
+      cp_ += sy;
+      gyp += sy;
+      gx += sx;
+      if (s + 1 < T) {                                 // next step's operands, a whole weight stream ahead of their use
+        load_step(s + 2 < T, uo0, n0);
+        load_step(s + 2 < T, uo1, n1);
+      }
+      float* mine = &part[w][0][lane * 4];
+      for (int tp = 0; tp < KS; ++tp) {
+        const bool odd = 2 * tp + 1 < NG;              // (wave-uniform: the last tile of an odd tile count is dead)
+        if (odd) lstm_wide_loadw(wb, wp + (size_t)(2 * tp + 1) * WSLOTS_CHUNK);
+        tile(wa, fh, fl, mine + (2 * tp) * 256);
+        lstm_wide_loadw(wa, wp + (size_t)(tp + 1 < KS ? 2 * tp + 2 : 0) * WSLOTS_CHUNK);      // wraps into the next step
+        if (odd) tile(wb, fh, fl, mine + (2 * tp + 1) * 256);
+      }
+      in0 = n0;
+      in1 = n1;
+    }
+    __syncthreads();
+    // dh of this wave's output tiles: the live waves' partial sums, in wave order
+    if (live0) {
+      f32x4_t s0 = *reinterpret_cast<const f32x4_t*>(&part[0][2 * w][lane * 4]);
+      for (int pw = 1; pw < KS; ++pw) s0 += *reinterpret_cast<const f32x4_t*>(&part[pw][2 * w][lane * 4]);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) dh_rec[0][r] = s0[r];
+      if (live1) {
+        f32x4_t s1 = *reinterpret_cast<const f32x4_t*>(&part[0][2 * w + 1][lane * 4]);
+        for (int pw = 1; pw < KS; ++pw) s1 += *reinterpret_cast<const f32x4_t*>(&part[pw][2 * w + 1][lane * 4]);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) dh_rec[1][r] = s1[r];
+      }
+    }
+    __syncthreads();                                   // every sum is read before the next step overwrites the buffer
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // Fused LSTM cell for the wide, short `multi2one` LSTM (hidden 300: W_hh does not fit one CU's registers, and the
 // sequences are only 1-3 real words long).  The recurrent product h W_hh^T is a plain GEMM per step; this kernel does the
 // whole pointwise part of a step in one pass over a ragged, length-sorted batch: rows < n_active are advanced, rows
@@ -593,6 +927,49 @@ extern "C" int ruart_lstm_bwd(const float* grad_y, const float* w_hh, const floa
   }
   hipLaunchKernelGGL(lstm_bwd_kernel, dim3(B, ndir), dim3(512), 0, (hipStream_t)stream, grad_y, w_hh, gates, cells, grad_xproj, T, h,
                      ndir);
+  RUART_CHECK_LAUNCH();
+  return 0;
+}
+
+// 128 < h <= 256: the streamed kernels.  The image of either pass is ndir x KS x KS chunk pairs of 16 KiB, KS = ceil(h / 32) - 1 MiB per
+// direction at h = 256, 400 KiB at h = 144; the transposed (backward) image has the same size, so one workspace serves either call.
+static bool lstm_wide_h_ok(int h) { return h > HP && h <= 256; }
+static size_t lstm_wide_image_bytes(int h, int ndir) {
+  const size_t KS = (size_t)(h + 31) / 32;
+  return (size_t)ndir * KS * KS * 2 * WSLOTS_CHUNK * 16;
+}
+
+extern "C" int ruart_lstm_wide_ws_bytes(int h, int ndir, int with_backward, size_t* bytes) {
+  if (!lstm_wide_h_ok(h) || ndir < 1 || ndir > 2 || !bytes) return (int)hipErrorInvalidValue;
+  (void)with_backward;      // (the backward call prepares its own image over the forward's: the larger of the two, and they are equal)
+  *bytes = lstm_wide_image_bytes(h, ndir);
+  return 0;
+}
+
+// Every argument is checked before the first launch; each call prepares its own image in ws (no allocation, no sync).
+extern "C" int ruart_lstm_wide_fwd(const float* xproj, const float* w_hh, float* y, float* gates, float* cells, float* hprev, int B, int T,
+                                   int h, int ndir, void* ws, size_t ws_bytes, void* stream) {
+  if (!lstm_wide_h_ok(h) || ndir < 1 || ndir > 2 || B <= 0 || T <= 0 || !ws || !xproj || !w_hh || !y) return (int)hipErrorInvalidValue;
+  if (ws_bytes < lstm_wide_image_bytes(h, ndir)) return (int)hipErrorInvalidValue;
+  RUART_ENTRY();
+  const int KS = (h + 31) / 32, total = ndir * KS * KS * 2 * WSLOTS_CHUNK;
+  hipLaunchKernelGGL(lstm_wide_prep_fwd_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, w_hh, (bf16x8_t*)ws, h, KS, total);
+  hipLaunchKernelGGL(lstm_wide_fwd_kernel, dim3((B + LRB - 1) / LRB, ndir), dim3(512), 0, (hipStream_t)stream, xproj, (const bf16x8_t*)ws, y,
+                     gates, cells, hprev, B, T, h, ndir, ruart_nan_flag_ptr);
+  RUART_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int ruart_lstm_wide_bwd(const float* grad_y, const float* w_hh, const float* gates, const float* cells, float* grad_xproj, int B,
+                                   int T, int h, int ndir, void* ws, size_t ws_bytes, void* stream) {
+  if (!lstm_wide_h_ok(h) || ndir < 1 || ndir > 2 || B <= 0 || T <= 0 || !ws || !grad_y || !w_hh || !gates || !cells || !grad_xproj)
+    return (int)hipErrorInvalidValue;
+  if (ws_bytes < lstm_wide_image_bytes(h, ndir)) return (int)hipErrorInvalidValue;
+  RUART_ENTRY();
+  const int KS = (h + 31) / 32, total = ndir * KS * KS * 2 * WSLOTS_CHUNK;
+  hipLaunchKernelGGL(lstm_wide_prep_bwd_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, w_hh, (bf16x8_t*)ws, h, KS, total);
+  hipLaunchKernelGGL(lstm_wide_bwd_kernel, dim3((B + LRB - 1) / LRB, ndir), dim3(512), 0, (hipStream_t)stream, grad_y, (const bf16x8_t*)ws, gates,
+                     cells, grad_xproj, B, T, h, ndir);
   RUART_CHECK_LAUNCH();
   return 0;
 }

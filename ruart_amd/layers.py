@@ -139,7 +139,7 @@ class StackedBRNN(nn.Module):
             rnn_input = hiddens[-1]
             if i == 1 and x_additional is not None:
                 rnn_input = torch.cat((rnn_input, x_additional), 2)
-            if self.hidden_size <= 128:
+            if self.hidden_size <= ops.LSTM_MAX_HIDDEN:
                 # the input dropout (Layers.py:160-164) is folded into the input projection and its two gradient GEMMs
                 mask = seq_dropout_mask(rnn_input, p=dropout_p, training=self.training)
                 if mask is None and dropout_p > 0:
@@ -169,8 +169,9 @@ def lstm_cell_steps(xproj_steps, w_hh, n_active, h0, c0, zero_state=True):
 
 
 def lstm_layer_wide(x, w_ih, w_hh, b_ih, b_hh, *reverse_params):
-    """Dense (B, T, D) LSTM for hidden sizes above the persistent kernel's 128 limit (multi2one, hidden 300, when it
-    is called through the generic module API).  T is short (<= max words per item)."""
+    """Dense (B, T, D) LSTM for hidden sizes above ``ops.LSTM_MAX_HIDDEN`` (256), the widest layer the persistent kernels take
+    (multi2one, hidden 300, when it is called through the generic module API): a Python loop over the T steps of each direction, one
+    ``ops.addmm`` and one fused cell kernel per step.  Meant for short T (<= max words per item)."""
     def run(w_ih, w_hh, b_ih, b_hh, rev):
         B, T, _ = x.shape
         xp = ops.linear(x, w_ih, b_ih + b_hh)

@@ -701,8 +701,28 @@ def linear16(x, w, b=None):
 
 
 # ---------------------------------------------------------------------------------------------------------
+LSTM_RESIDENT_HIDDEN = 128      # up to here W_hh stays in registers for the whole sequence (ruart_lstm_fwd / _bwd)
+LSTM_MAX_HIDDEN = 256           # up to here the recurrence is one persistent launch: above 128 it streams W_hh (ruart_lstm_wide_fwd / _bwd)
+
+
+_lstm_wide_bytes = {}           # (h, ndir) -> ruart_lstm_wide_ws_bytes
+
+
+def _lstm_wide_workspace(h, ndir, device):
+    """Workspace of ONE ruart_lstm_wide_fwd / _bwd call.  An ordinary allocation per call, not ``_scratch``: the trunk's streams run
+    LSTM layers concurrently, and a shared buffer would be rewritten under a running kernel."""
+    n = _lstm_wide_bytes.get((h, ndir))
+    if n is None:
+        out = ctypes.c_size_t()
+        hip.kernels().ruart_lstm_wide_ws_bytes(h, ndir, 1, ctypes.byref(out))
+        n = _lstm_wide_bytes[(h, ndir)] = out.value
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
 class _LstmRecurrence(torch.autograd.Function):
-    """Sequential part of one (Bi)LSTM layer.  xproj (B,T,ndir*4h) already holds x W_ih^T + b_ih + b_hh."""
+    """Sequential part of one (Bi)LSTM layer.  xproj (B,T,ndir*4h) already holds x W_ih^T + b_ih + b_hh.  Hidden sizes up to
+    LSTM_RESIDENT_HIDDEN run the register-resident kernels, up to LSTM_MAX_HIDDEN the streamed ones; wider layers are refused by the
+    library (HipError)."""
 
     @staticmethod
     def forward(ctx, xproj, w_hh, ndir):
@@ -723,7 +743,11 @@ class _LstmRecurrence(torch.autograd.Function):
                 if t is not None:
                     t.zero_()
         else:
-            lib.ruart_lstm_fwd(xproj, w_hh, y, gates, cells, hprev, B, T, h, ndir, hip.stream_ptr())
+            if h > LSTM_RESIDENT_HIDDEN:
+                ws = _lstm_wide_workspace(h, ndir, xproj.device)
+                lib.ruart_lstm_wide_fwd(xproj, w_hh, y, gates, cells, hprev, B, T, h, ndir, ws, ws.numel(), hip.stream_ptr())
+            else:
+                lib.ruart_lstm_fwd(xproj, w_hh, y, gates, cells, hprev, B, T, h, ndir, hip.stream_ptr())
         ctx.ndir, ctx.h = ndir, h
         ctx.mode = trunk_grad_gemm if trunk_gemm == "x3" else trunk_gemm
         ctx.save_for_backward(w_hh, gates, cells, hprev)
@@ -741,7 +765,11 @@ class _LstmRecurrence(torch.autograd.Function):
         if "lstm" in _ABL_SKIP:
             gx.zero_()
         else:
-            lib.ruart_lstm_bwd(gy, w_hh, gates, cells, gx, B, T, h, ndir, hip.stream_ptr())
+            if h > LSTM_RESIDENT_HIDDEN:
+                ws = _lstm_wide_workspace(h, ndir, gy.device)
+                lib.ruart_lstm_wide_bwd(gy, w_hh, gates, cells, gx, B, T, h, ndir, ws, ws.numel(), hip.stream_ptr())
+            else:
+                lib.ruart_lstm_bwd(gy, w_hh, gates, cells, gx, B, T, h, ndir, hip.stream_ptr())
         # grad_W_hh[d] = sum_{b,t} da[b,t,d] (x) h_prev[b,t,d]: one GEMM per direction on column slices (strided views, no copies)
         gw = None
         if ctx.needs_input_grad[1]:
