@@ -473,30 +473,26 @@ int ruart_scorer_heads_bwd(const float* x, const float* u1, const float* u2, con
  *   cells : (B, T, ndir*h)   c_t                       }
  *   hprev : (B, T, ndir*h)   h of the previous step of the same direction (0 at its first step): the right-hand operand of
  *                            grad_W_hh = grad_xproj^T . hprev, so the caller needs no shifted copy of y
- * h <= 128, ndir in {1, 2} (hipErrorInvalidValue otherwise; 128 < h <= 256: ruart_lstm_wide_fwd / _bwd below). */
-/* Kernel form of ruart_lstm_fwd / ruart_lstm_bwd: 1 (default) = 16 batch rows per workgroup, the recurrent product on the matrix cores
+ * One entry pair for every hidden size 1 <= h <= 256, ndir in {1, 2}; the calls choose the kernels.  Up to h = 128 W_hh stays in a CU's
+ * registers for the whole sequence and no workspace is needed: ruart_lstm_ws_bytes writes 0, `ws` may be NULL and ws_bytes is ignored.
+ * Above that each call first writes W_hh - split into bf16 hi / lo, in MFMA fragment order - into the caller's workspace `ws`
+ * (>= ruart_lstm_ws_bytes(h, ndir), 16-byte aligned) and the persistent kernel streams that image from L2 every step.  Each of the two
+ * calls prepares its own image (they may be given different workspaces; one size serves both); `ws` must stay untouched until the call's
+ * kernels have run.  No allocation, no sync.  Tensors, arithmetic and the NaN flag are the same at every size.
+ * hipErrorInvalidValue - before anything is launched or the device is touched - for h or ndir outside these ranges, B <= 0, T <= 0, a
+ * NULL xproj / w_hh / y (forward) or grad_y / w_hh / gates / cells / grad_xproj (backward), a NULL `bytes`, and, where a workspace is
+ * needed, a NULL ws or ws_bytes too small.
+ * BPTT: grad_y (B,T,ndir*h) -> grad_xproj (B,T,ndir*4h) (gradient w.r.t. the gate pre-activations).  grad_W_hh = grad_xproj^T . h_prev,
+ * grad_W_ih = grad_xproj^T . x, grad_x = grad_xproj . W_ih are plain GEMMs done by the caller.
+ * ruart_lstm_set_variant: kernel form for h <= 128: 1 (default) = 16 batch rows per workgroup, the recurrent product on the matrix cores
  * with split-bf16 operands (hi.hi + hi.lo + lo.hi, fp32 accumulation - the arithmetic of ruart_gemm_x3), B * ndir / 16 workgroups;
- * 0 = one workgroup per (row, direction) with exact fp32 FMAs (rounds 1-2).  Process-wide. */
+ * 0 = one workgroup per (row, direction) with exact fp32 FMAs (rounds 1-2; always taken for h < 4).  Process-wide. */
 int ruart_lstm_set_variant(int variant);
+int ruart_lstm_ws_bytes(int h, int ndir, size_t* bytes);
 int ruart_lstm_fwd(const float* xproj, const float* w_hh, float* y, float* gates, float* cells, float* hprev, int B, int T, int h,
-                   int ndir, void* stream);
-/* BPTT for the op above: grad_y (B,T,ndir*h) -> grad_xproj (B,T,ndir*4h) (gradient w.r.t. the gate pre-activations).
- * grad_W_hh = grad_xproj^T . h_prev, grad_W_ih = grad_xproj^T . x, grad_x = grad_xproj . W_ih are plain GEMMs done
- * by the caller. */
+                   int ndir, void* ws, size_t ws_bytes, void* stream);
 int ruart_lstm_bwd(const float* grad_y, const float* w_hh, const float* gates, const float* cells, float* grad_xproj, int B,
-                   int T, int h, int ndir, void* stream);
-
-/* The same recurrence and BPTT for 128 < h <= 256, same tensors, arithmetic and NaN flag: W_hh does not fit a CU's registers there, so each
- * call first writes it - split into bf16 hi / lo, in MFMA fragment order - into the caller's workspace `ws` (>= ruart_lstm_wide_ws_bytes,
- * 16-byte aligned) and the persistent kernel streams that image from L2 every step.  Each of the two calls prepares its own image (they may
- * be given different workspaces); `ws` must stay untouched until the call's kernels have run.  No allocation, no sync.
- * hipErrorInvalidValue - before anything is launched - for h <= 128, h > 256, ndir outside {1, 2}, B <= 0, T <= 0, a NULL ws or
- * ws_bytes too small.  ws_bytes(with_backward = 1) serves either call. */
-int ruart_lstm_wide_ws_bytes(int h, int ndir, int with_backward, size_t* bytes);
-int ruart_lstm_wide_fwd(const float* xproj, const float* w_hh, float* y, float* gates, float* cells, float* hprev, int B, int T, int h,
-                        int ndir, void* ws, size_t ws_bytes, void* stream);
-int ruart_lstm_wide_bwd(const float* grad_y, const float* w_hh, const float* gates, const float* cells, float* grad_xproj, int B,
-                        int T, int h, int ndir, void* ws, size_t ws_bytes, void* stream);
+                   int T, int h, int ndir, void* ws, size_t ws_bytes, void* stream);
 
 /* The operands of one BIDIRECTIONAL nn.LSTM layer (Models/Layers.py:124-180 via nn.LSTM; torch's parameter layout, G = 4h gate rows) in
  * one launch: w (2G, K) = [w_ih ; w_ih_reverse] for the input projection of both directions, b (2G) = [b_ih + b_hh ; the reverse pair],
@@ -509,7 +505,7 @@ int ruart_lstm_pack_params(const float* w_ih, const float* w_ih_r, const float* 
  * variational dropout of a packed (words, D) matrix with one mask row per item (layers.row_dropout; Models/Layers.py:23-30). */
 int ruart_rows_scale(const float* x, int ldx, const float* mask, int ldm, const long long* row_of, float* out, int ldo, int rows, int D,
                      void* stream);
-/* Pointwise part of ONE step of a wide LSTM over a ragged, length-sorted batch (the `multi2one` LSTM, Models/SDNet.py:137,
+/* Pointwise part of ONE step of an LSTM stepped by the caller over a ragged, length-sorted batch (the `multi2one` LSTM, Models/SDNet.py:137,
  * 269-271: hidden 300, 1-3 real words per item).  pre (n_active, 4h) = x W_ih^T + b + h_prev W_hh^T from the caller's GEMMs;
  * rows < n_active are advanced (acts (n_active,4h) = post-activation i,f,g,o saved for backward), rows >= n_active of
  * h_out / c_out (n_rows, h) copy h_prev / c_prev.  Backward: grad_h / grad_c (may be NULL = zero) -> grad_pre (n_active,4h),

@@ -5,15 +5,22 @@
 // (Models/SDNet.py:147, 150, 172, 188; Models/Layers.py:489), T up to 100 sequential steps: latency-bound.
 //
 // The input projection x W_ih^T + b_ih + b_hh for all time steps and both directions is ONE plain GEMM done by the
-// caller (xproj).  This file is the sequential part: one workgroup per (batch row, direction) keeps its direction's
+// caller (xproj).  This file is the sequential part.  In its first form one workgroup per (batch row, direction) keeps its direction's
 // W_hh (4h x h, <= 512 x 128 fp32 = 256 KB) entirely in VGPRs - 128 weights per thread - for the whole sequence, the
 // running h in LDS (broadcast reads), c in a register.  Two barriers per step, no global traffic for weights.
 // Backward (BPTT) is the mirror image with W_hh^T columns in VGPRs; it emits grad_xproj, from which the caller gets
 // grad_W_ih, grad_b, grad_x and grad_W_hh with three plain GEMMs.
+//
+// Three kernel pairs serve ONE entry pair, ruart_lstm_fwd / _bwd (below the streamed pair): the per-row pair that follows, the MFMA
+// pair (16 batch rows per workgroup; the default) and, for HP < h <= LSTM_MAX_H, the streamed pair.  The fused cell of the Python-stepped
+// route for still larger hidden sizes and the parameter packing come last, each with its entry points.
 #include "common.h"
 #include "ruart_hip.h"
 
-#define HP 128      // padded hidden size (h <= 128)
+#define HP 128      // padded hidden size of the resident kernels: up to here W_hh stays in registers for the whole sequence
+#define LSTM_MAX_H 256      // largest hidden size of the streamed kernels, and so of ruart_lstm_fwd / _bwd
+
+extern int* ruart_nan_flag_ptr;
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
@@ -458,7 +465,7 @@ __global__ __launch_bounds__(512) void lstm_bwd_mfma_kernel(const float* __restr
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// The same recurrence for 128 < h <= 256 (ruart_lstm_wide_fwd / _bwd): the weights are STREAMED.
+// The same recurrence for HP < h <= LSTM_MAX_H: the weights are STREAMED.
 //
 // At h = 256 the bf16 hi / lo image of one direction's W_hh is 4 . 256 . 256 . 4 B = 1 MiB: neither a CU's registers (512 KiB) nor its
 // LDS (160 KiB) hold it.  Everything else is lstm_fwd_mfma_kernel's: one workgroup owns 16 batch rows of one direction for the whole
@@ -792,6 +799,77 @@ __global__ __launch_bounds__(512) void lstm_wide_bwd_kernel(const float* __restr
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// Entry points of the recurrence: one pair for every hidden size 1 .. LSTM_MAX_H.  They choose the kernels: h <= HP the resident ones
+// (ruart_lstm_set_variant: MFMA or per-row; h < 4 is always per-row), above it the streamed ones behind their preparation kernel.
+// ---------------------------------------------------------------------------------------------------------
+static int g_lstm_variant = 1;       // 1: 16 batch rows per workgroup on the matrix cores (default); 0: one workgroup per row, fp32 VALU
+extern "C" int ruart_lstm_set_variant(int v) {
+  if (v != 0 && v != 1) return (int)hipErrorInvalidValue;
+  g_lstm_variant = v;
+  return 0;
+}
+
+// Workspace of one call, or false for sizes the recurrence does not take.  The resident kernels need none.  The streamed image of either
+// pass is ndir x KS x KS chunk pairs of 16 KiB, KS = ceil(h / 32) - 1 MiB per direction at h = 256, 400 KiB at h = 144; the transposed
+// (backward) image has the same size, and each call prepares its own, so one workspace serves either call.
+static bool lstm_ws_bytes(int h, int ndir, size_t* bytes) {
+  if (h < 1 || h > LSTM_MAX_H || ndir < 1 || ndir > 2) return false;
+  const size_t KS = (size_t)(h + 31) / 32;
+  *bytes = h <= HP ? 0 : (size_t)ndir * KS * KS * 2 * WSLOTS_CHUNK * 16;
+  return true;
+}
+
+extern "C" int ruart_lstm_ws_bytes(int h, int ndir, size_t* bytes) {
+  return bytes && lstm_ws_bytes(h, ndir, bytes) ? 0 : (int)hipErrorInvalidValue;
+}
+
+// What both calls check besides their own pointers, before they touch the device: the sizes, and a workspace where one is needed.
+static bool lstm_sizes_ok(int B, int T, int h, int ndir, const void* ws, size_t ws_bytes) {
+  size_t need;
+  return B > 0 && T > 0 && lstm_ws_bytes(h, ndir, &need) && (need == 0 || (ws && ws_bytes >= need));
+}
+
+extern "C" int ruart_lstm_fwd(const float* xproj, const float* w_hh, float* y, float* gates, float* cells, float* hprev, int B, int T,
+                              int h, int ndir, void* ws, size_t ws_bytes, void* stream) {
+  if (!lstm_sizes_ok(B, T, h, ndir, ws, ws_bytes) || !xproj || !w_hh || !y) return (int)hipErrorInvalidValue;
+  RUART_ENTRY();
+  if (h > HP) {      // the image is prepared in ws by every call: no allocation, no sync
+    const int KS = (h + 31) / 32, total = ndir * KS * KS * 2 * WSLOTS_CHUNK;
+    hipLaunchKernelGGL(lstm_wide_prep_fwd_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, w_hh, (bf16x8_t*)ws, h, KS, total);
+    hipLaunchKernelGGL(lstm_wide_fwd_kernel, dim3((B + LRB - 1) / LRB, ndir), dim3(512), 0, (hipStream_t)stream, xproj, (const bf16x8_t*)ws, y,
+                       gates, cells, hprev, B, T, h, ndir, ruart_nan_flag_ptr);
+  } else if (g_lstm_variant == 1 && h >= 4) {
+    hipLaunchKernelGGL(lstm_fwd_mfma_kernel, dim3((B + LRB - 1) / LRB, ndir), dim3(512), 0, (hipStream_t)stream, xproj, w_hh, y, gates, cells,
+                       hprev, B, T, h, ndir, ruart_nan_flag_ptr);
+  } else {
+    hipLaunchKernelGGL(lstm_fwd_kernel, dim3(B, ndir), dim3(512), 0, (hipStream_t)stream, xproj, w_hh, y, gates, cells, hprev, T, h, ndir,
+                       ruart_nan_flag_ptr);
+  }
+  RUART_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int ruart_lstm_bwd(const float* grad_y, const float* w_hh, const float* gates, const float* cells, float* grad_xproj, int B,
+                              int T, int h, int ndir, void* ws, size_t ws_bytes, void* stream) {
+  if (!lstm_sizes_ok(B, T, h, ndir, ws, ws_bytes) || !grad_y || !w_hh || !gates || !cells || !grad_xproj) return (int)hipErrorInvalidValue;
+  RUART_ENTRY();
+  if (h > HP) {
+    const int KS = (h + 31) / 32, total = ndir * KS * KS * 2 * WSLOTS_CHUNK;
+    hipLaunchKernelGGL(lstm_wide_prep_bwd_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, w_hh, (bf16x8_t*)ws, h, KS, total);
+    hipLaunchKernelGGL(lstm_wide_bwd_kernel, dim3((B + LRB - 1) / LRB, ndir), dim3(512), 0, (hipStream_t)stream, grad_y, (const bf16x8_t*)ws, gates,
+                       cells, grad_xproj, B, T, h, ndir);
+  } else if (g_lstm_variant == 1 && h >= 4) {
+    hipLaunchKernelGGL(lstm_bwd_mfma_kernel, dim3((B + LRB - 1) / LRB, ndir), dim3(512), 0, (hipStream_t)stream, grad_y, w_hh, gates, cells,
+                       grad_xproj, B, T, h, ndir);
+  } else {
+    hipLaunchKernelGGL(lstm_bwd_kernel, dim3(B, ndir), dim3(512), 0, (hipStream_t)stream, grad_y, w_hh, gates, cells, grad_xproj, T, h,
+                       ndir);
+  }
+  RUART_CHECK_LAUNCH();
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // Fused LSTM cell for the wide, short `multi2one` LSTM (hidden 300: W_hh does not fit one CU's registers, and the
 // sequences are only 1-3 real words long).  The recurrent product h W_hh^T is a plain GEMM per step; this kernel does the
 // whole pointwise part of a step in one pass over a ragged, length-sorted batch: rows < n_active are advanced, rows
@@ -851,7 +929,30 @@ __global__ __launch_bounds__(256) void lstm_cell_bwd_kernel(const float* __restr
   }
 }
 
-extern int* ruart_nan_flag_ptr;
+extern "C" int ruart_lstm_cell_fwd(const float* pre, const float* h_prev, const float* c_prev, float* h_out, float* c_out,
+                                   float* acts, int n_active, int n_rows, int h, void* stream) {
+  RUART_ENTRY();
+  if (n_rows <= 0 || h <= 0 || n_active < 0 || n_active > n_rows) return (int)hipErrorInvalidValue;
+  const long long total = (long long)n_rows * h;
+  const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+  hipLaunchKernelGGL(lstm_cell_fwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, pre, h_prev, c_prev, h_out, c_out, acts,
+                     n_active, n_rows, h);
+  RUART_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int ruart_lstm_cell_bwd(const float* grad_h, const float* grad_c, const float* acts, const float* c_prev,
+                                   const float* c_out, float* grad_pre, float* grad_h_prev, float* grad_c_prev, int n_active,
+                                   int n_rows, int h, void* stream) {
+  RUART_ENTRY();
+  if (n_rows <= 0 || h <= 0 || n_active < 0 || n_active > n_rows) return (int)hipErrorInvalidValue;
+  const long long total = (long long)n_rows * h;
+  const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+  hipLaunchKernelGGL(lstm_cell_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, grad_h, grad_c, acts, c_prev, c_out,
+                     grad_pre, grad_h_prev, grad_c_prev, n_active, n_rows, h);
+  RUART_CHECK_LAUNCH();
+  return 0;
+}
 
 // The operands one bidirectional nn.LSTM layer's kernels take, assembled from its eight parameter tensors in ONE launch (torch: two
 // cats, two adds and a stack - five launches per layer and step, 55 of a step's ~900):
@@ -888,235 +989,6 @@ extern "C" int ruart_lstm_pack_params(const float* w_ih, const float* w_ih_r, co
   const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
   hipLaunchKernelGGL(lstm_pack_params_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w_ih, w_ih_r, b_ih, b_hh, b_ih_r, b_hh_r, w_hh,
                      w_hh_r, w, b, whh, n_w, n_hh, G);
-  RUART_CHECK_LAUNCH();
-  return 0;
-}
-
-static int g_lstm_variant = 1;       // 1: 16 batch rows per workgroup on the matrix cores (default); 0: one workgroup per row, fp32 VALU
-extern "C" int ruart_lstm_set_variant(int v) {
-  if (v != 0 && v != 1) return (int)hipErrorInvalidValue;
-  g_lstm_variant = v;
-  return 0;
-}
-
-extern "C" int ruart_lstm_fwd(const float* xproj, const float* w_hh, float* y, float* gates, float* cells, float* hprev, int B, int T,
-                              int h, int ndir, void* stream) {
-  RUART_ENTRY();
-  if (B <= 0 || T <= 0 || h <= 0 || h > HP || ndir < 1 || ndir > 2) return (int)hipErrorInvalidValue;
-  if (g_lstm_variant == 1 && h >= 4) {
-    hipLaunchKernelGGL(lstm_fwd_mfma_kernel, dim3((B + LRB - 1) / LRB, ndir), dim3(512), 0, (hipStream_t)stream, xproj, w_hh, y, gates, cells,
-                       hprev, B, T, h, ndir, ruart_nan_flag_ptr);
-    RUART_CHECK_LAUNCH();
-    return 0;
-  }
-  hipLaunchKernelGGL(lstm_fwd_kernel, dim3(B, ndir), dim3(512), 0, (hipStream_t)stream, xproj, w_hh, y, gates, cells, hprev, T, h, ndir,
-                     ruart_nan_flag_ptr);
-  RUART_CHECK_LAUNCH();
-  return 0;
-}
-
-extern "C" int ruart_lstm_bwd(const float* grad_y, const float* w_hh, const float* gates, const float* cells, float* grad_xproj,
-                              int B, int T, int h, int ndir, void* stream) {
-  RUART_ENTRY();
-  if (B <= 0 || T <= 0 || h <= 0 || h > HP || ndir < 1 || ndir > 2) return (int)hipErrorInvalidValue;
-  if (g_lstm_variant == 1 && h >= 4) {
-    hipLaunchKernelGGL(lstm_bwd_mfma_kernel, dim3((B + LRB - 1) / LRB, ndir), dim3(512), 0, (hipStream_t)stream, grad_y, w_hh, gates, cells,
-                       grad_xproj, B, T, h, ndir);
-    RUART_CHECK_LAUNCH();
-    return 0;
-  }
-  hipLaunchKernelGGL(lstm_bwd_kernel, dim3(B, ndir), dim3(512), 0, (hipStream_t)stream, grad_y, w_hh, gates, cells, grad_xproj, T, h,
-                     ndir);
-  RUART_CHECK_LAUNCH();
-  return 0;
-}
-
-// 128 < h <= 256: the streamed kernels.  The image of either pass is ndir x KS x KS chunk pairs of 16 KiB, KS = ceil(h / 32) - 1 MiB per
-// direction at h = 256, 400 KiB at h = 144; the transposed (backward) image has the same size, so one workspace serves either call.
-static bool lstm_wide_h_ok(int h) { return h > HP && h <= 256; }
-static size_t lstm_wide_image_bytes(int h, int ndir) {
-  const size_t KS = (size_t)(h + 31) / 32;
-  return (size_t)ndir * KS * KS * 2 * WSLOTS_CHUNK * 16;
-}
-
-extern "C" int ruart_lstm_wide_ws_bytes(int h, int ndir, int with_backward, size_t* bytes) {
-  if (!lstm_wide_h_ok(h) || ndir < 1 || ndir > 2 || !bytes) return (int)hipErrorInvalidValue;
-  (void)with_backward;      // (the backward call prepares its own image over the forward's: the larger of the two, and they are equal)
-  *bytes = lstm_wide_image_bytes(h, ndir);
-  return 0;
-}
-
-// Every argument is checked before the first launch; each call prepares its own image in ws (no allocation, no sync).
-extern "C" int ruart_lstm_wide_fwd(const float* xproj, const float* w_hh, float* y, float* gates, float* cells, float* hprev, int B, int T,
-                                   int h, int ndir, void* ws, size_t ws_bytes, void* stream) {
-  if (!lstm_wide_h_ok(h) || ndir < 1 || ndir > 2 || B <= 0 || T <= 0 || !ws || !xproj || !w_hh || !y) return (int)hipErrorInvalidValue;
-  if (ws_bytes < lstm_wide_image_bytes(h, ndir)) return (int)hipErrorInvalidValue;
-  RUART_ENTRY();
-  const int KS = (h + 31) / 32, total = ndir * KS * KS * 2 * WSLOTS_CHUNK;
-  hipLaunchKernelGGL(lstm_wide_prep_fwd_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, w_hh, (bf16x8_t*)ws, h, KS, total);
-  hipLaunchKernelGGL(lstm_wide_fwd_kernel, dim3((B + LRB - 1) / LRB, ndir), dim3(512), 0, (hipStream_t)stream, xproj, (const bf16x8_t*)ws, y,
-                     gates, cells, hprev, B, T, h, ndir, ruart_nan_flag_ptr);
-  RUART_CHECK_LAUNCH();
-  return 0;
-}
-
-extern "C" int ruart_lstm_wide_bwd(const float* grad_y, const float* w_hh, const float* gates, const float* cells, float* grad_xproj, int B,
-                                   int T, int h, int ndir, void* ws, size_t ws_bytes, void* stream) {
-  if (!lstm_wide_h_ok(h) || ndir < 1 || ndir > 2 || B <= 0 || T <= 0 || !ws || !grad_y || !w_hh || !gates || !cells || !grad_xproj)
-    return (int)hipErrorInvalidValue;
-  if (ws_bytes < lstm_wide_image_bytes(h, ndir)) return (int)hipErrorInvalidValue;
-  RUART_ENTRY();
-  const int KS = (h + 31) / 32, total = ndir * KS * KS * 2 * WSLOTS_CHUNK;
-  hipLaunchKernelGGL(lstm_wide_prep_bwd_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, w_hh, (bf16x8_t*)ws, h, KS, total);
-  hipLaunchKernelGGL(lstm_wide_bwd_kernel, dim3((B + LRB - 1) / LRB, ndir), dim3(512), 0, (hipStream_t)stream, grad_y, (const bf16x8_t*)ws, gates,
-                     cells, grad_xproj, B, T, h, ndir);
-  RUART_CHECK_LAUNCH();
-  return 0;
-}
-
-// ------------------------------------------------------------------------------------------------
-// out[w][c] = x[w][c] * m[idx[w]][c]: the variational dropout of a PACKED (words, D) matrix whose mask is drawn per (item, feature)
-// (layers.row_dropout; Models/Layers.py:23-30 on the reference's padded (items, Lw, D) layout).  One pass instead of torch's gather of the
-// mask rows into a (words, D) matrix followed by a multiply (3x the traffic); the backward is the same kernel on the gradient.
-// One wave per row, four 16-byte loads in flight per lane; D % 4 == 0, rows 16-byte aligned.
-__global__ __launch_bounds__(256) void rows_scale_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ m, int ldm,
-                                                         const long long* __restrict__ idx, float* __restrict__ out, int ldo, int rows, int D) {
-  const int lane = threadIdx.x & 63;
-  const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (w >= rows) return;
-  const float* xr = x + (size_t)w * ldx;
-  const float* mr = m + (size_t)idx[w] * ldm;
-  float* orow = out + (size_t)w * ldo;
-  for (int c0 = lane * 4; c0 < D; c0 += 4 * 256) {
-    f32x4_t a[4], b[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int c = min(c0 + u * 256, D - 4);                 // clamped: every load is unconditional
-      a[u] = load4(xr + c);
-      b[u] = load4(mr + c);
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-      if (c0 + u * 256 < D) store4(orow + c0 + u * 256, a[u] * b[u]);
-  }
-}
-
-extern "C" int ruart_rows_scale(const float* x, int ldx, const float* mask, int ldm, const long long* row_of, float* out, int ldo, int rows,
-                                int D, void* stream) {
-  RUART_ENTRY();
-  if (rows <= 0 || D < 4 || (D & 3) || (ldx & 3) || (ldm & 3) || (ldo & 3) || !x || !mask || !row_of || !out) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(rows_scale_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, ldx, mask, ldm, row_of, out, ldo, rows, D);
-  RUART_CHECK_LAUNCH();
-  return 0;
-}
-
-extern "C" int ruart_lstm_cell_fwd(const float* pre, const float* h_prev, const float* c_prev, float* h_out, float* c_out,
-                                   float* acts, int n_active, int n_rows, int h, void* stream) {
-  RUART_ENTRY();
-  if (n_rows <= 0 || h <= 0 || n_active < 0 || n_active > n_rows) return (int)hipErrorInvalidValue;
-  const long long total = (long long)n_rows * h;
-  const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-  hipLaunchKernelGGL(lstm_cell_fwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, pre, h_prev, c_prev, h_out, c_out, acts,
-                     n_active, n_rows, h);
-  RUART_CHECK_LAUNCH();
-  return 0;
-}
-
-extern "C" int ruart_lstm_cell_bwd(const float* grad_h, const float* grad_c, const float* acts, const float* c_prev,
-                                   const float* c_out, float* grad_pre, float* grad_h_prev, float* grad_c_prev, int n_active,
-                                   int n_rows, int h, void* stream) {
-  RUART_ENTRY();
-  if (n_rows <= 0 || h <= 0 || n_active < 0 || n_active > n_rows) return (int)hipErrorInvalidValue;
-  const long long total = (long long)n_rows * h;
-  const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-  hipLaunchKernelGGL(lstm_cell_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, grad_h, grad_c, acts, c_prev, c_out,
-                     grad_pre, grad_h_prev, grad_c_prev, n_active, n_rows, h);
-  RUART_CHECK_LAUNCH();
-  return 0;
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// Embedding weight gradient from a HOST-prepared sort (Models/SDNet.py:439-493 looks words / POS / entity ids up in
-// nn.Embedding tables; torch's backward sorts the ids on the device every step - ~100 launches and ~1 ms for the step's nine
-// lookups).  The ids of a batch are known when it is collated, so ruart_amd.batch.BatchIndex sorts them there (numpy, in the
-// loader worker): order[] lists the lookup positions grouped by table row, seg_start[s] .. seg_start[s+1] is the slice of
-// order[] that hit row seg_row[s].  One workgroup per distinct row adds its gradient rows in that fixed order (no atomics:
-// deterministic); rows that were never looked up keep the zero the caller filled gw with.
-// A row with very many occurrences (a frequent word; [CLS], [SEP] and the first positions of the trainable encoder's tables: thousands
-// per batch) would be one long chain of dependent loads in one workgroup, so the host cuts such rows into sub-segments of <= 64
-// occurrences (batch._sort_ids): ruart_embedding_bwd_split sums the sub-segments into a workspace with this kernel (seg_row == NULL:
-// segment s -> row s) and then the sub-segment sums of each row into gw with it again (order == NULL: occurrence i is workspace row i).
-// ---------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void embedding_bwd_sorted_kernel(const float* __restrict__ gy, const int* __restrict__ order,
-                                                                   const int* __restrict__ seg_start, const int* __restrict__ seg_row,
-                                                                   float* __restrict__ gw, int D, int dpad) {
-  __shared__ float red[256];
-  const int s = blockIdx.x, tid = threadIdx.x;
-  const int beg = seg_start[s], end = seg_start[s + 1];
-  float* dst = gw + (size_t)(seg_row ? seg_row[s] : s) * D;
-  const int G = 256 / dpad;                     // occurrence groups working side by side on narrow tables (dpad = 8..256)
-  const int g = tid / dpad, dl = tid % dpad;
-  if (G == 1) {
-    // wide tables (D > 128; blockIdx.y = chunk of 256 columns): a frequent row - the position table of the trainable encoder has 64
-    // rows with ~700 occurrences each - is a chain of dependent loads, so eight occurrences are in flight per lane and the eight partial
-    // sums are combined in a fixed order
-    const int d = blockIdx.y * 256 + tid;
-    if (d >= D) return;
-    float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    int i = beg;
-    for (; i + 7 < end; i += 8) {
-      int o[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) o[k] = order ? order[i + k] : i + k;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) a[k] += gy[(size_t)o[k] * D + d];
-    }
-    for (int k = 0; i < end; ++i, ++k) a[k] += gy[(size_t)(order ? order[i] : i) * D + d];
-    dst[d] = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
-    return;
-  }
-  for (int d0 = 0; d0 < D; d0 += dpad) {
-    const int d = d0 + dl;
-    float acc = 0.f;
-    if (d < D)
-      for (int i = beg + g; i < end; i += G) acc += gy[(size_t)(order ? order[i] : i) * D + d];
-    __syncthreads();
-    red[tid] = acc;
-    __syncthreads();
-    if (g == 0 && d < D) {
-      float t = 0.f;
-      for (int q = 0; q < G; ++q) t += red[q * dpad + dl];          // fixed order
-      dst[d] = t;
-    }
-  }
-}
-
-static void launch_embedding_bwd(const float* gy, const int* order, const int* seg_start, const int* seg_row, int n_seg, int D, float* out,
-                                 hipStream_t stream) {
-  int dpad = 8;
-  while (dpad < D && dpad < 256) dpad <<= 1;
-  hipLaunchKernelGGL(embedding_bwd_sorted_kernel, dim3(n_seg, dpad == 256 ? (D + 255) / 256 : 1), dim3(256), 0, stream, gy, order, seg_start,
-                     seg_row, out, D, dpad);
-}
-
-extern "C" int ruart_embedding_bwd_sorted(const float* grad_out, const int* order, const int* seg_start, const int* seg_row, int n_seg,
-                                          int D, float* grad_weight, void* stream) {
-  RUART_ENTRY();
-  if (n_seg < 0 || D <= 0 || D > 4096 || (n_seg && (!order || !seg_start || !seg_row))) return (int)hipErrorInvalidValue;
-  if (n_seg == 0) return 0;
-  launch_embedding_bwd(grad_out, order, seg_start, seg_row, n_seg, D, grad_weight, (hipStream_t)stream);
-  RUART_CHECK_LAUNCH();
-  return 0;
-}
-
-extern "C" int ruart_embedding_bwd_split(const float* grad_out, const int* order, const int* sub_start, int n_sub, const int* row_first,
-                                         const int* row_id, int n_rows, int D, float* ws, float* grad_weight, void* stream) {
-  RUART_ENTRY();
-  if (n_sub < 0 || n_rows < 0 || n_rows > n_sub || D <= 0 || D > 4096 || (n_sub && (!order || !sub_start || !row_first || !row_id || !ws)))
-    return (int)hipErrorInvalidValue;
-  if (n_sub == 0) return 0;
-  launch_embedding_bwd(grad_out, order, sub_start, nullptr, n_sub, D, ws, (hipStream_t)stream);          // ws[s] = sum of sub-segment s
-  launch_embedding_bwd(ws, nullptr, row_first, row_id, n_rows, D, grad_weight, (hipStream_t)stream);      // gw[row] = its sub-segments, in order
   RUART_CHECK_LAUNCH();
   return 0;
 }

@@ -103,7 +103,8 @@ def row_dropout(x, rows_of, n_rows, p, training):
 
 class StackedBRNN(nn.Module):
     """Layers.py:124-180.  ``rnns`` holds nn.LSTM modules purely as parameter containers (identical names, shapes and
-    initialisation to the reference); the recurrence itself runs in ruart_lstm_fwd/bwd."""
+    initialisation to the reference).  Hidden sizes up to ``ops.LSTM_MAX_HIDDEN`` run the persistent recurrence (ruart_lstm_fwd /
+    _bwd, one launch per layer and pass); larger ones are stepped from Python (lstm_layer_stepped)."""
 
     def __init__(self, input_size, hidden_size, num_layers, rnn_type=nn.LSTM, concat_layers=False, bidirectional=True,
                  add_feat=0, LN=False, batch_size=None, max_len=None):
@@ -148,7 +149,7 @@ class StackedBRNN(nn.Module):
             else:
                 if dropout_p > 0:
                     rnn_input = dropout(rnn_input, p=dropout_p, training=self.training)
-                out = lstm_layer_wide(rnn_input, *self.layer_params(i))
+                out = lstm_layer_stepped(rnn_input, *self.layer_params(i))
             if LN:
                 out = ops.whole_layer_norm(out, group=ln_group)
             hiddens.append(out)
@@ -157,7 +158,7 @@ class StackedBRNN(nn.Module):
 
 
 def lstm_cell_steps(xproj_steps, w_hh, n_active, h0, c0, zero_state=True):
-    """Step a (wide) LSTM over a ragged, length-sorted batch: at step s only the first n_active[s] rows are alive.
+    """Step an LSTM of any hidden size from Python over a ragged, length-sorted batch: at step s only the first n_active[s] rows are alive.
     xproj_steps[s] is (n_active[s], 4h).  Per step: one GEMM (recurrent product, fused with the add of xproj) and one
     fused HIP cell kernel.  Returns the final (h, c) of every row."""
     h, c = h0, c0
@@ -168,9 +169,9 @@ def lstm_cell_steps(xproj_steps, w_hh, n_active, h0, c0, zero_state=True):
     return h, c
 
 
-def lstm_layer_wide(x, w_ih, w_hh, b_ih, b_hh, *reverse_params):
-    """Dense (B, T, D) LSTM for hidden sizes above ``ops.LSTM_MAX_HIDDEN`` (256), the widest layer the persistent kernels take
-    (multi2one, hidden 300, when it is called through the generic module API): a Python loop over the T steps of each direction, one
+def lstm_layer_stepped(x, w_ih, w_hh, b_ih, b_hh, *reverse_params):
+    """Dense (B, T, D) LSTM stepped from Python, for hidden sizes above ``ops.LSTM_MAX_HIDDEN``, the largest the persistent kernels
+    take (multi2one, hidden 300, when it is called through the generic module API): a loop over the T steps of each direction, one
     ``ops.addmm`` and one fused cell kernel per step.  Meant for short T (<= max words per item)."""
     def run(w_ih, w_hh, b_ih, b_hh, rev):
         B, T, _ = x.shape

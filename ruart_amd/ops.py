@@ -553,8 +553,8 @@ class _Linear(torch.autograd.Function):
 
 
 class _AddMM(torch.autograd.Function):
-    """base + x W^T in one launch (the residual rides in the GEMM epilogue): the recurrent product of the wide `multi2one` LSTM
-    step added to the step's input projection (Models/SDNet.py:269-271 via nn.LSTM)."""
+    """base + x W^T in one launch (the residual rides in the GEMM epilogue): the recurrent product of a Python-stepped LSTM
+    step (`multi2one`) added to the step's input projection (Models/SDNet.py:269-271 via nn.LSTM)."""
 
     @staticmethod
     def forward(ctx, base, x, w):
@@ -701,28 +701,26 @@ def linear16(x, w, b=None):
 
 
 # ---------------------------------------------------------------------------------------------------------
-LSTM_RESIDENT_HIDDEN = 128      # up to here W_hh stays in registers for the whole sequence (ruart_lstm_fwd / _bwd)
-LSTM_MAX_HIDDEN = 256           # up to here the recurrence is one persistent launch: above 128 it streams W_hh (ruart_lstm_wide_fwd / _bwd)
+LSTM_MAX_HIDDEN = 256           # up to here the recurrence is one persistent launch (ruart_lstm_fwd / _bwd); StackedBRNN routes by it
+
+_lstm_ws_bytes = {}             # (h, ndir) -> ruart_lstm_ws_bytes
 
 
-_lstm_wide_bytes = {}           # (h, ndir) -> ruart_lstm_wide_ws_bytes
-
-
-def _lstm_wide_workspace(h, ndir, device):
-    """Workspace of ONE ruart_lstm_wide_fwd / _bwd call.  An ordinary allocation per call, not ``_scratch``: the trunk's streams run
-    LSTM layers concurrently, and a shared buffer would be rewritten under a running kernel."""
-    n = _lstm_wide_bytes.get((h, ndir))
+def _lstm_workspace(h, ndir, device):
+    """Workspace of ONE ruart_lstm_fwd / _bwd call, or None where the library needs none (W_hh resident in registers).  An ordinary
+    allocation per call, not ``_scratch``: the trunk's streams run LSTM layers concurrently, and a shared buffer would be rewritten
+    under a running kernel."""
+    n = _lstm_ws_bytes.get((h, ndir))
     if n is None:
         out = ctypes.c_size_t()
-        hip.kernels().ruart_lstm_wide_ws_bytes(h, ndir, 1, ctypes.byref(out))
-        n = _lstm_wide_bytes[(h, ndir)] = out.value
-    return torch.empty(n, dtype=torch.uint8, device=device)
+        hip.kernels().ruart_lstm_ws_bytes(h, ndir, ctypes.byref(out))
+        n = _lstm_ws_bytes[(h, ndir)] = out.value
+    return torch.empty(n, dtype=torch.uint8, device=device) if n else None
 
 
 class _LstmRecurrence(torch.autograd.Function):
-    """Sequential part of one (Bi)LSTM layer.  xproj (B,T,ndir*4h) already holds x W_ih^T + b_ih + b_hh.  Hidden sizes up to
-    LSTM_RESIDENT_HIDDEN run the register-resident kernels, up to LSTM_MAX_HIDDEN the streamed ones; wider layers are refused by the
-    library (HipError)."""
+    """Sequential part of one (Bi)LSTM layer.  xproj (B,T,ndir*4h) already holds x W_ih^T + b_ih + b_hh.  The library chooses the
+    kernels by the hidden size; layers above LSTM_MAX_HIDDEN are refused by it (HipError)."""
 
     @staticmethod
     def forward(ctx, xproj, w_hh, ndir):
@@ -743,11 +741,8 @@ class _LstmRecurrence(torch.autograd.Function):
                 if t is not None:
                     t.zero_()
         else:
-            if h > LSTM_RESIDENT_HIDDEN:
-                ws = _lstm_wide_workspace(h, ndir, xproj.device)
-                lib.ruart_lstm_wide_fwd(xproj, w_hh, y, gates, cells, hprev, B, T, h, ndir, ws, ws.numel(), hip.stream_ptr())
-            else:
-                lib.ruart_lstm_fwd(xproj, w_hh, y, gates, cells, hprev, B, T, h, ndir, hip.stream_ptr())
+            ws = _lstm_workspace(h, ndir, xproj.device)
+            lib.ruart_lstm_fwd(xproj, w_hh, y, gates, cells, hprev, B, T, h, ndir, ws, ws.numel() if ws is not None else 0, hip.stream_ptr())
         ctx.ndir, ctx.h = ndir, h
         ctx.mode = trunk_grad_gemm if trunk_gemm == "x3" else trunk_gemm
         ctx.save_for_backward(w_hh, gates, cells, hprev)
@@ -765,11 +760,8 @@ class _LstmRecurrence(torch.autograd.Function):
         if "lstm" in _ABL_SKIP:
             gx.zero_()
         else:
-            if h > LSTM_RESIDENT_HIDDEN:
-                ws = _lstm_wide_workspace(h, ndir, gy.device)
-                lib.ruart_lstm_wide_bwd(gy, w_hh, gates, cells, gx, B, T, h, ndir, ws, ws.numel(), hip.stream_ptr())
-            else:
-                lib.ruart_lstm_bwd(gy, w_hh, gates, cells, gx, B, T, h, ndir, hip.stream_ptr())
+            ws = _lstm_workspace(h, ndir, gy.device)
+            lib.ruart_lstm_bwd(gy, w_hh, gates, cells, gx, B, T, h, ndir, ws, ws.numel() if ws is not None else 0, hip.stream_ptr())
         # grad_W_hh[d] = sum_{b,t} da[b,t,d] (x) h_prev[b,t,d]: one GEMM per direction on column slices (strided views, no copies)
         gw = None
         if ctx.needs_input_grad[1]:

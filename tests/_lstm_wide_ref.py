@@ -1,4 +1,4 @@
-"""References for the streamed LSTM recurrence (128 < h <= 256; ruart_lstm_wide_fwd / _bwd), shared by test_lstm_wide_ref.py (CPU) and
+"""References for the streamed LSTM recurrence (128 < h <= 256 of ruart_lstm_fwd / _bwd), shared by test_lstm_wide_ref.py (CPU) and
 test_gpu_lstm_wide.py (GPU).
 
   reference64(shape)  one nn.LSTM layer (batch_first, zero state, gate order i, f, g, o, padding not masked) and its BPTT gradients,

@@ -719,15 +719,16 @@ def test_fused_lstm_cell_ragged():
     assert maxerr(bd.grad[n:], b.grad[n:]) < 1e-6 and float(bd.grad[:n].abs().max()) == 0.0
 
 
-def test_wide_lstm_module_path():
-    """StackedBRNN with hidden > 128 (the generic multi2one module API) on the fused cell + library GEMMs."""
+def test_stepped_lstm_layer():
+    """layers.lstm_layer_stepped (the route StackedBRNN takes above ops.LSTM_MAX_HIDDEN) on a StackedBRNN's parameters: the fused
+    cell + library GEMMs, one Python step per time step, forward and backward against torch's nn.LSTM."""
     import ruart_amd.layers as L
     d = dev()
     L.set_dropout_prob(0.0)
     torch.manual_seed(0)
     m = L.StackedBRNN(20, 150, 1, bidirectional=True).to(d)
     x = torch.randn(4, 5, 20, device=d, requires_grad=True)
-    y = m(x, None)
+    y = L.lstm_layer_stepped(x, *m.layer_params(0))
     ref_m = torch.nn.LSTM(20, 150, batch_first=True, bidirectional=True)
     ref_m.load_state_dict({k.replace("rnns.0.", ""): v.cpu() for k, v in m.state_dict().items()})
     xc = x.detach().cpu().requires_grad_()

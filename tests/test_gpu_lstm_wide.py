@@ -1,4 +1,4 @@
-"""The streamed LSTM recurrence for 128 < hidden <= 256 on the MI355X (ruart_lstm_wide_fwd / _bwd through ops.lstm_layer and
+"""The streamed LSTM recurrence for 128 < hidden <= 256 on the MI355X (ruart_lstm_fwd / _bwd's streamed kernels through ops.lstm_layer and
 layers.StackedBRNN): against the float64 restatement of tests/_lstm_wide_ref.py at the bounds test_lstm_layer holds the resident
 kernels to, the forward-only call, the NaN flag, the module's routing, and SDNet end to end at hidden_size 144 against the unmodified
 reference (tests/golden/sdnet_e2e_hidden144.npz, written by tools/gen_golden_hidden.py)."""
@@ -87,12 +87,12 @@ class _SteppedRoute(Exception):
 
 
 def test_stacked_brnn_routes_up_to_256_to_the_persistent_kernels(monkeypatch):
-    """hidden_size 144: forward and backward never touch the stepped route (layers.lstm_layer_wide); hidden_size 300 still takes it."""
+    """hidden_size 144: forward and backward never touch the stepped route (layers.lstm_layer_stepped); hidden_size 300 still takes it."""
     import ruart_amd.layers as L
 
     def refuse(*a, **k):
         raise _SteppedRoute()
-    monkeypatch.setattr(L, "lstm_layer_wide", refuse)
+    monkeypatch.setattr(L, "lstm_layer_stepped", refuse)
     L.set_dropout_prob(0.0)
     torch.manual_seed(0)
     m = L.StackedBRNN(20, 144, 2, bidirectional=True).to(DEV)
@@ -165,7 +165,7 @@ def test_sdnet_hidden144_forward_backward_vs_reference(golden, bert_weights, pre
 
 
 def test_hidden144_three_stream_schedule_is_bit_equal_to_one_stream(golden, bert_weights):
-    """opt['ruart_streams'] on and off: the same kernels on the same operands - each wide LSTM call with a workspace of its own -, so
+    """opt['ruart_streams'] on and off: the same kernels on the same operands - each streamed LSTM call with a workspace of its own -, so
     the forward scores are bit-equal; the gradients of both stay within the fixture's bound (x3: 1e-2)."""
     z = golden
     net, opt = _net(z, bert_weights, bert_precision="x3")

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Persistent LSTM recurrence kernels: time per call and per step at the trunk's shapes."""
+"""Persistent LSTM recurrence (ruart_lstm_fwd / _bwd, both resident variants): time per call and per step at the trunk's shapes,
+forward only and forward + backward.  The streamed widths (hidden 129-256) are timed by tools/lstm_wide_time.py."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ruart_amd import ops

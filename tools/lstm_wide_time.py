@@ -1,13 +1,13 @@
 #!/usr/bin/env python3
 """Time one bidirectional LSTM layer, forward + backward, on the streamed persistent kernels (ops.lstm_layer, 128 < hidden <= 256)
-against the stepped route (layers.lstm_layer_wide: one GEMM and one cell kernel per time step and direction).
+against the stepped route (layers.lstm_layer_stepped: one GEMM and one cell kernel per time step and direction).
 
     python tools/lstm_wide_time.py time [--runs 25] [--warmup 5] [--resources FILE] [--out profiles/lstm_wide.txt]     (needs the GPU)
     python tools/lstm_wide_time.py resources                                                                          (needs hipcc only)
 
 ``time``: both routes alternate in one process on the same seeded operands; after the warm-up every run is timed with device events,
 and the report gives the median, the fastest and the slowest run and the 10th / 90th percentile of each route, the median per time
-step (layer time / T) and the ratio of the medians.  ``resources`` prints the register, scratch and LDS use of the wide kernels as
+step (layer time / T) and the ratio of the medians.  ``resources`` prints the register, scratch and LDS use of the streamed kernels as
 hipcc reports them; ``--resources FILE`` copies such a listing into the report.
 """
 import argparse
@@ -63,7 +63,7 @@ def time_routes(runs, warmup):
         x = torch.randn(B, T, Din, generator=g).to(dev).requires_grad_()
         gy = torch.randn(B, T, 2 * h, generator=g).to(dev)
         routes = {"streamed (ops.lstm_layer)": lambda: ops.lstm_layer(x, *P),
-                  "stepped (layers.lstm_layer_wide)": lambda: L.lstm_layer_wide(x, *P)}
+                  "stepped (layers.lstm_layer_stepped)": lambda: L.lstm_layer_stepped(x, *P)}
         outs, times = {}, {n: [] for n in routes}
         for it in range(warmup + runs):
             for name, fn in routes.items():
@@ -79,7 +79,7 @@ def time_routes(runs, warmup):
                     times[name].append(e0.elapsed_time(e1) * 1e3)
                 outs[name] = y.detach()
         ops.nan_flag.check_and_clear()
-        diff = float((outs["streamed (ops.lstm_layer)"] - outs["stepped (layers.lstm_layer_wide)"]).abs().max())
+        diff = float((outs["streamed (ops.lstm_layer)"] - outs["stepped (layers.lstm_layer_stepped)"]).abs().max())
         lines.append("(B, T, D_in, hidden) = (%d, %d, %d, %d), bidirectional, forward + backward, %d timed runs after %d warm-up, us"
                      % (B, T, Din, h, runs, warmup))
         med = {}
@@ -88,7 +88,7 @@ def time_routes(runs, warmup):
             med[name] = float(np.median(ts))
             lines.append("  %-34s median %9.1f   min %9.1f   p10 %9.1f   p90 %9.1f   max %9.1f   per step (median / T) %7.2f"
                          % (name, med[name], ts.min(), np.percentile(ts, 10), np.percentile(ts, 90), ts.max(), med[name] / T))
-        a, b = med["streamed (ops.lstm_layer)"], med["stepped (layers.lstm_layer_wide)"]
+        a, b = med["streamed (ops.lstm_layer)"], med["stepped (layers.lstm_layer_stepped)"]
         lines.append("  stepped / streamed = %.2f   (max |y_streamed - y_stepped| = %.2e)" % (b / a, diff))
         # the recurrence alone: forward kernel time per step, the figure the streamed design was estimated by
         xp = ops.linear(x.detach(), torch.cat([P[0], P[4]], 0), torch.cat([P[2] + P[3], P[6] + P[7]], 0)).contiguous()
