@@ -21,6 +21,7 @@
 #ifndef RUART_HIP_H
 #define RUART_HIP_H
 #include <stddef.h>
+#include <stdint.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -534,6 +535,18 @@ int ruart_embedding_bwd_split(const float* grad_out, const int* order, const int
  * raises: here `status` (device int, zero it first; may be NULL) receives 1 + the index of one offending word and that character
  * is skipped.  An empty word gives a zero row. */
 int ruart_phoc_table(const unsigned char* chars, const int* offsets, int n_words, float* out, int ldo, int* status, void* stream);
+
+/* Answer-string metrics (Utils/eval_func.py:13-24 the Levenshtein distance of the ANLS score, :62-68 the equality count of the VQA
+ * accuracy) for a batch of string pairs in one launch.  Strings are code points: string s is chars[str_off[s] .. str_off[s+1])
+ * (str_off holds n_str + 1 offsets into the n_chars code points); pair p is (pair_a[p], pair_b[p]).  dist[p] = unit-cost edit distance,
+ * equal[p] = 1 when the two strings are identical, else 0.  The strings are compared as given (lower-casing is the caller's).
+ * Checked on the host before any launch (hipErrorInvalidValue): a null pointer, a negative count, n_str == 0 with n_pairs > 0;
+ * n_pairs == 0 returns 0 and launches nothing.  Checked in the kernel for each pair, whatever the index arrays hold: both string
+ * indices in [0, n_str), both offset pairs inside [0, n_chars] and ordered, both lengths <= RUART_EDIT_MAX_LEN - a pair that fails
+ * gets dist = -1, equal = 0 and nothing is read through it (longer strings are the caller's: ruart_amd.metrics scores them on the host). */
+#define RUART_EDIT_MAX_LEN 128
+int ruart_edit_distance_pairs(const int32_t* chars, int n_chars, const int32_t* str_off, int n_str, const int32_t* pair_a,
+                              const int32_t* pair_b, int n_pairs, int32_t* dist, int32_t* equal, void* stream);
 
 /* Optimizer step (Models/SDNetTrainer.py:366-367: clip_grad_norm_(params, grad_clipping) then Adamax.step()) over all trainable
  * tensors in three launches.  `grads` / `params` / `exp_avg` / `exp_inf` are DEVICE arrays of device pointers (one per tensor);

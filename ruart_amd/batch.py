@@ -80,7 +80,14 @@ class VQA_collate:
         od_f = [f["od"] for f in flats] if ocr_f is not None else None
         ocr_list = self.item_collate([t.get("ocr") for t in batch], o["max_ocr_len"], o["max_ocr_bert_len"], o["max_ocr_num"], ocr_f)
         od_list = self.item_collate([t.get("od") for t in batch], o["max_od_len"], o["max_od_bert_len"], o["max_od_num"], od_f)
-        gt_list = self.gt_collate([t["gt"] for t in batch])
+        if o.get("label_from_answers") and all(t["gt"] is None for t in batch):
+            # records without precomputed scores: no target tensor; the strings the labels are scored from are packed here (in the
+            # loader's workers) and ``SDNetTrainer.ToCUDA`` uploads them and builds the target on the device
+            from .metrics import pack_label_table
+            gt_list = None
+            q_list["_ruart_label_pack"] = pack_label_table([t["extra_info"] for t in batch], o)
+        else:
+            gt_list = self.gt_collate([t["gt"] for t in batch])
         if self.prepare_index:
             q_list["_ruart_host_index"] = BatchIndex(q_list, ocr_list, od_list, o)
         return q_list, ocr_list, od_list, gt_list, [t["extra_info"] for t in batch]

@@ -269,6 +269,10 @@ class VQA_Dataset(Dataset):
     # -- soft labels (VQA_Dataset.py:211-290) -------------------------------------------------------------------
     def get_label(self, ocr_list, q_id=None, answers=None):
         if self.score_name not in ocr_list[0]:
+            if self.opt.get("label_from_answers"):
+                # no host label: ``VQA_collate`` packs the strings and ``SDNetTrainer.ToCUDA`` builds the target on the device from
+                # the answers (metrics.labels_from_table - this method's rule, restated for tensors)
+                return None
             return None, None                            # (sic) the reference returns a pair when the records carry no scores
         gt = [t[self.score_name] for t in ocr_list]
         n_ynu = 0

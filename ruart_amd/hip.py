@@ -169,6 +169,7 @@ _SIGNATURES = {
     "ruart_embedding_bwd_sorted": (_I, [_P, _P, _P, _P, _I, _I, _P, _P]),
     "ruart_embedding_bwd_split": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _P, _P, _P]),
     "ruart_phoc_table": (_I, [_P, _P, _I, _P, _I, _P, _P]),
+    "ruart_edit_distance_pairs": (_I, [_P, _I, _P, _I, _P, _P, _I, _P, _P, _P]),
     "ruart_gemm_bf16_tn": (_I, [_P, _LL, _P, _LL, _P, _I, _I, _I, _I, _P, _SZ, _P]),
     "ruart_gemm_x3_tn_grouped_ws": (_SZ, [POINTER(X3TnProblemC), _I]),
     "ruart_gemm_x3_tn_grouped": (_I, [POINTER(X3TnProblemC), _I, _P, _SZ, _P]),

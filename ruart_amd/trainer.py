@@ -33,6 +33,7 @@ import torch.optim as optim
 
 from . import layers as L
 from .batch import VQA_collate, to_device
+from .metrics import FRONT_ANSWERS as _FRONT_ANSWERS         # the no_read / yes / no slots of ``label_yesno``, in slot order
 from .sampler import VQA_Sampler, merge_rank_shards
 from .sdnet import SDNet
 
@@ -111,13 +112,62 @@ class AverageMeter:
         self.avg = self.sum / self.count
 
 
-def decode_predictions(scores, num_cnt, extra_info, opt):
+def _credit(a, c, n_answers):
+    """What one decoded answer adds to the ANLS / ACC sums (Models/SDNetTrainer.py:441-446): the ten-answers rule and the 0.5 floor."""
+    return (a if a >= 0.5 else 0), (min(c * 10 / 3.0, 1) if n_answers == 10 else min(c * 10, 1))
+
+
+def _slot_metrics(scores, idx, valid, cnt, n_front, extra_info, want_bound):
+    """The metric values of a decode on the GPU: the (candidate x answer) table of the batch once (metrics.answer_table: one launch of
+    ``ruart_edit_distance_pairs``), the chosen slot's ANLS / ACC gathered on the device and brought back with the chosen index in ONE
+    readback.  Sample b's candidates are the front answers, its ``ocr_list`` strings and "unanswerable": slot s decodes to candidate s
+    while s < n_front + num_cnt, to "unanswerable" behind that - the decode's own rule.  ``want_bound``: also the best credit over the
+    admitted slots (``valid``, plus the fallback slot when nothing is admissible).  -> rows [idx, anls, acc (, best ANLS credit, best
+    ACC credit)] as python floats."""
+    from .metrics import answer_table
+    dev = scores.device
+    n_ocr = [len(e["ocr_list"]) for e in extra_info]
+    for i, e in enumerate(extra_info):                       # (the host path's ocr_list[idx] raises the same way)
+        if int(cnt[i]) > n_ocr[i]:
+            raise IndexError("sample %d: num_cnt %d exceeds its %d ocr_list strings" % (i, int(cnt[i]), n_ocr[i]))
+    front = list(_FRONT_ANSWERS[:n_front])
+    anls, acc = answer_table([front + list(e["ocr_list"]) + ["unanswerable"] for e in extra_info], [e["answers"] for e in extra_info], dev)
+    ar = torch.arange(scores.shape[1], device=dev).unsqueeze(0)
+    cnt_t = torch.as_tensor([int(c) for c in cnt], device=dev).unsqueeze(1)
+    last = torch.as_tensor(n_ocr, device=dev).unsqueeze(1) + n_front
+    cand = torch.where(ar < n_front + cnt_t, ar, last)
+    slot_anls, slot_acc = anls.gather(1, cand), acc.gather(1, cand)
+    pick = idx.unsqueeze(1)
+    cols = [idx.double(), slot_anls.gather(1, pick).squeeze(1), slot_acc.gather(1, pick).squeeze(1)]
+    if want_bound:
+        adm = valid.scatter(1, pick, True)
+        ten = torch.as_tensor([e["answers"] is not None and len(e["answers"]) == 10 for e in extra_info], device=dev).unsqueeze(1)
+        zero = torch.zeros((), dtype=torch.float64, device=dev)
+        a = torch.where(slot_anls >= 0.5, slot_anls, zero)
+        three = torch.full((), 3.0, dtype=torch.float64, device=dev)        # (a tensor divisor: a scalar one becomes a reciprocal product)
+        c = torch.where(ten, (slot_acc * 10 / three).clamp(max=1), (slot_acc * 10).clamp(max=1))
+        cols += [torch.where(adm, a, zero).max(dim=1).values, torch.where(adm, c, zero).max(dim=1).values]
+    return torch.stack(cols, dim=1).cpu().tolist()
+
+
+def _host_bound(valid_row, idx, answer_of, answers):
+    """The CPU path of ``opt['eval_upper_bound']`` for one sample: the best credit over the admitted slots, with the host functions."""
+    from .metrics import note_stvqa, note_textvqa
+    slots = [s for s, v in enumerate(valid_row) if v or s == idx]
+    got = [_credit(note_stvqa(answers, answer_of(s)), note_textvqa(answers, answer_of(s)), len(answers)) for s in slots]
+    return max(g[0] for g in got), max(g[1] for g in got)
+
+
+def decode_predictions(scores, num_cnt, extra_info, opt, bound=None):
     """The answer decode of Models/SDNetTrainer.py:391-450 for scores (B, n_slots) on any device: per sample the reference walks
     the slots by descending score, skips the ``<OCR>`` sentinel and the padding slots (>= num_cnt), stops at the first real OCR
     token - or at the no-answer slot (last column, ``label_no_answer``) if that comes first.  A descending walk that stops at the
     first admissible slot is a masked arg-max, done here in one device op for the batch.  When nothing is admissible the
     reference's loop runs out and is left with the LOWEST-scored slot; that case is reproduced too.
-    Returns (ANLS sum, ACC sum, res, save_res) as the reference's ``predict`` does after the loss."""
+    Returns (ANLS sum, ACC sum, res, save_res) as the reference's ``predict`` does after the loss.  Scores on the GPU: the per-sample
+    metric values come out of the batch's answer table (``_slot_metrics``) instead of ``note_stvqa`` / ``note_textvqa`` calls per sample;
+    they are the same floats, and they are added up here in sample order as before.  ``bound`` (a list, ``opt['eval_upper_bound']``)
+    receives per sample the best (ANLS, ACC) credit any admitted slot would have earned, None for a sample without answers."""
     from .metrics import note_stvqa, note_textvqa
     if "label_yesno" in opt or "fixed_answers" in opt:
         raise NotImplementedError("yes/no and fixed-answer slots are outside the accelerated path (SURVEY section 8)")
@@ -130,32 +180,42 @@ def decode_predictions(scores, num_cnt, extra_info, opt):
     if no_answer:
         valid[:, -1] = True
     best = scores.masked_fill(~valid, -1.0).argmax(dim=1)
-    idxs = torch.where(valid.any(dim=1), best, scores.argmin(dim=1)).cpu().tolist()
+    idx_t = torch.where(valid.any(dim=1), best, scores.argmin(dim=1))
+    rows = _slot_metrics(scores, idx_t, valid, num_cnt, 0, extra_info, bound is not None) if scores.is_cuda else None
+    idxs = [int(r[0]) for r in rows] if rows is not None else idx_t.cpu().tolist()
+    valid_h = valid.tolist() if bound is not None and rows is None else None
     prob = scores.detach().cpu()
     res, save_res, ANLS, ACC = [], [], 0, 0
     for i, idx in enumerate(idxs):
-        answer = extra_info[i]["ocr_list"][idx] if idx < int(num_cnt[i]) else "unanswerable"
+        def answer_of(s):
+            return extra_info[i]["ocr_list"][s] if s < int(num_cnt[i]) else "unanswerable"
+        answer = answer_of(idx)
         res.append({"question_id": extra_info[i]["q_id"], "answer": answer})
         save_res.append({"question_id": extra_info[i]["q_id"], "prediction": answer, "answers": extra_info[i]["answers"],
                          "score": prob[i, idx].item(), "idx": idx, "ids_len": n_slots, "ocr_list": extra_info[i]["ocr_list"]})
         if extra_info[i]["answers"] is not None:
-            a = note_stvqa(extra_info[i]["answers"], answer)
-            c = note_textvqa(extra_info[i]["answers"], answer)
+            if rows is None:
+                a = note_stvqa(extra_info[i]["answers"], answer)
+                c = note_textvqa(extra_info[i]["answers"], answer)
+            else:
+                a, c = rows[i][1], rows[i][2]
             ACC += min(c * 10 / 3.0, 1) if len(extra_info[i]["answers"]) == 10 else min(c * 10, 1)
             ANLS += a if a >= 0.5 else 0
+            if bound is not None:
+                bound.append(tuple(rows[i][3:5]) if rows is not None else _host_bound(valid_h[i], idx, answer_of, extra_info[i]["answers"]))
+        elif bound is not None:
+            bound.append(None)
     return ANLS, ACC, res, save_res
 
 
-_FRONT_ANSWERS = ("answering does not require reading text in the image", "yes", "no")
-
-
-def decode_slots(scores, num_cnt, extra_info, opt):
+def decode_slots(scores, num_cnt, extra_info, opt, bound=None):
     """``decode_predictions`` for the layout of ``label_yesno``: scores (B, 3 + n_ocr_slots (+ 1)) with the no_read / yes / no slots in
     front (Models/SDNetTrainer.py:396-448 with fixed_answers_len = 0, yesno_num = 3), again as one masked arg-max on the device.
     A slot is admissible when idx < 3 + num_cnt - or it is the no-answer slot (last column, ``label_no_answer``), where the walk stops
     first - and idx != len(ocr_list) - 1.  Both of the reference's quirks are kept (sic): that sentinel test is not offset by the three
     front slots, so slot len(ocr_list) - 1 - a real OCR item (or a front slot) - is skipped, and slot 3 + num_cnt - 1, the ``<OCR>``
-    sentinel itself, is admissible and decodes to "<OCR>".  Nothing admissible: the lowest-scored slot, as in ``decode_predictions``."""
+    sentinel itself, is admissible and decodes to "<OCR>".  Nothing admissible: the lowest-scored slot, as in ``decode_predictions``.
+    Scores on the GPU and ``bound``: as in ``decode_predictions``."""
     from .metrics import note_stvqa, note_textvqa
     if "fixed_answers" in opt:
         raise NotImplementedError("fixed-answer slots are outside the accelerated path (SURVEY section 8)")
@@ -169,24 +229,35 @@ def decode_slots(scores, num_cnt, extra_info, opt):
     if no_answer:
         valid[:, -1] = True                      # (tested before the skip: the walk stops there even when it is the skipped index)
     best = scores.masked_fill(~valid, -1.0).argmax(dim=1)
-    idxs = torch.where(valid.any(dim=1), best, scores.argmin(dim=1)).cpu().tolist()
+    idx_t = torch.where(valid.any(dim=1), best, scores.argmin(dim=1))
+    rows = _slot_metrics(scores, idx_t, valid, num_cnt, front, extra_info, bound is not None) if scores.is_cuda else None
+    idxs = [int(r[0]) for r in rows] if rows is not None else idx_t.cpu().tolist()
+    valid_h = valid.tolist() if bound is not None and rows is None else None
     prob = scores.detach().cpu()
     res, save_res, ANLS, ACC = [], [], 0, 0
     for i, idx in enumerate(idxs):
-        if idx < front:
-            answer = _FRONT_ANSWERS[idx]
-        elif idx < front + int(num_cnt[i]):
-            answer = extra_info[i]["ocr_list"][idx - front]
-        else:
-            answer = "unanswerable"
+        def answer_of(s):
+            if s < front:
+                return _FRONT_ANSWERS[s]
+            if s < front + int(num_cnt[i]):
+                return extra_info[i]["ocr_list"][s - front]
+            return "unanswerable"
+        answer = answer_of(idx)
         res.append({"question_id": extra_info[i]["q_id"], "answer": answer})
         save_res.append({"question_id": extra_info[i]["q_id"], "prediction": answer, "answers": extra_info[i]["answers"],
                          "score": prob[i, idx].item(), "idx": idx, "ids_len": n_slots, "ocr_list": extra_info[i]["ocr_list"]})
         if extra_info[i]["answers"] is not None:
-            a = note_stvqa(extra_info[i]["answers"], answer)
-            c = note_textvqa(extra_info[i]["answers"], answer)
+            if rows is None:
+                a = note_stvqa(extra_info[i]["answers"], answer)
+                c = note_textvqa(extra_info[i]["answers"], answer)
+            else:
+                a, c = rows[i][1], rows[i][2]
             ACC += min(c * 10 / 3.0, 1) if len(extra_info[i]["answers"]) == 10 else min(c * 10, 1)
             ANLS += a if a >= 0.5 else 0
+            if bound is not None:
+                bound.append(tuple(rows[i][3:5]) if rows is not None else _host_bound(valid_h[i], idx, answer_of, extra_info[i]["answers"]))
+        elif bound is not None:
+            bound.append(None)
     return ANLS, ACC, res, save_res
 
 
@@ -385,6 +456,11 @@ class SDNetTrainer(BaseTrainer):
         out = to_device(batch, self.device)
         if "_ruart_index" in q:
             out[0]["_ruart_index"] = q["_ruart_index"]
+        pack = out[0].pop("_ruart_label_pack", None)
+        if pack is not None and out[3] is None:
+            # opt['label_from_answers']: the collate packed the strings (batch.VQA_collate); upload, one launch, the label rule in tensors
+            from .metrics import labels_from_pack
+            out[3] = labels_from_pack(pack, self.opt, self.device)
         return out
 
     def instance_bce_with_logits(self, logits, labels):
@@ -598,7 +674,12 @@ class SDNetTrainer(BaseTrainer):
             loss = self.loss_func(scores, gt_list).item() if gt_list is not None else 0
         self.network.check_nan()
         decode = decode_slots if "label_yesno" in self.opt else decode_predictions
-        ANLS, ACC, res, save_res = decode(scores, ocr_list["num_cnt"], extra_info, self.opt)
+        if self.opt.get("eval_upper_bound"):
+            # per sample the best credit any admitted slot would have earned; ``_evaluate`` collects them (the return value stays)
+            self._bound_rows = []
+            ANLS, ACC, res, save_res = decode(scores, ocr_list["num_cnt"], extra_info, self.opt, bound=self._bound_rows)
+        else:
+            ANLS, ACC, res, save_res = decode(scores, ocr_list["num_cnt"], extra_info, self.opt)
         return loss, ANLS, ACC, res, save_res
 
     def _is_main(self):
@@ -643,6 +724,9 @@ class SDNetTrainer(BaseTrainer):
                                                     world_size=world)) if is_dataset else val_data
         loss = ANLS = ACC = n = nb = 0
         res, save_res = [], []
+        want_bound = bool(self.opt.get("eval_upper_bound"))
+        b_anls = b_acc = 0
+        self.__dict__.pop("eval_bound", None)
         it = iter(loader)
         nxt = next(it, None)
         nxt = self.ToCUDA(nxt) if nxt is not None else None
@@ -652,6 +736,10 @@ class SDNetTrainer(BaseTrainer):
             nxt = self.ToCUDA(nxt) if nxt is not None else None       # lookahead: the next batch's encoder pass runs beside this trunk
             l, a, c, r, sr = self.predict(batch, next_batch=nxt)
             loss, ANLS, ACC, n, nb = loss + l, ANLS + a, ACC + c, n + len(r), nb + 1
+            if want_bound:
+                for row in self._bound_rows:              # in sample order, as the ANLS / ACC sums are formed
+                    if row is not None:
+                        b_anls, b_acc = b_anls + row[0], b_acc + row[1]
             res.extend(r)
             save_res.extend(sr)
         if world > 1:
@@ -662,8 +750,17 @@ class SDNetTrainer(BaseTrainer):
             loss = loss / world                         # the loss of a global batch is the mean of its W equal shards' losses
             res = merge_rank_shards([p[3] for p in parts], self.batch_size)
             save_res = merge_rank_shards([p[4] for p in parts], self.batch_size)
+            if want_bound:
+                parts = [None] * world
+                torch.distributed.all_gather_object(parts, (b_anls, b_acc), group=self.process_group)
+                b_anls, b_acc = sum(p[0] for p in parts), sum(p[1] for p in parts)
         n_items = len(val_data) if is_dataset else n
         loss, ANLS, ACC = loss / max(nb, 1), ANLS / max(n_items, 1), ACC / max(n_items, 1)
+        if want_bound:
+            # opt['eval_upper_bound']: what a perfect scorer could reach over the slots the decode admits - the OCR upper bound
+            self.eval_bound = {"ANLS": b_anls / max(n_items, 1), "ACC": b_acc / max(n_items, 1)}
+            log.info("Dataset: %s Batch: %7d OCR upper bound ANLS: %.3f ACC: %.3f", mode, batch_i, self.eval_bound["ANLS"],
+                     self.eval_bound["ACC"])
         if not is_dataset or not self._is_main():
             return loss, ANLS, ACC, res
         if mode == "test":
