@@ -41,7 +41,10 @@ const char* ruart_version(void);
  *      Models/Layers.py:226-227 for the fp32 form) --------------------------------------------------------
  * C[M,N] = act(A[M,K] . W[N,K]^T + bias[N]) + residual[M,N]
  * 16-bit form (in_dtype = BF16 or F16): M % 128 == 0, N % 128 == 0, K % 64 == 0 (the caller pads M; BERT's N, K always
- *            qualify); residual_dtype / out_dtype are in_dtype or F32; GELU and residual are exclusive. */
+ *            qualify); residual_dtype / out_dtype are in_dtype or F32; GELU and residual are exclusive.
+ *            Row pitches in elements: lda, ldw % 8 == 0 and >= K (the operands are read 16 bytes at a time), ldc % 4 == 0 and >= N, and
+ *            with a residual ldr % 4 == 0 and >= N (the epilogue moves four elements at a time); A, W, C non-NULL, M, N, K > 0.
+ *            Anything else returns hipErrorInvalidValue before a launch.  Columns past K / N of a row are neither read nor written. */
 int ruart_gemm_16_nt(const void* A, int lda, const void* W, int ldw, const float* bias, const void* residual, int ldr,
                      int residual_dtype, void* C, int ldc, int out_dtype, int M, int N, int K, int act, int in_dtype,
                      void* stream);
@@ -59,7 +62,9 @@ int ruart_gemm_16_nt_ws(const void* A, int lda, const void* W, int ldw, const fl
  * ~2^-16 relative operand error instead of the 2^-12 of a plain f16 product, at 2x (not 3x) the matrix time.
  *   act NONE: C (M, N) fp32, optional fp32 residual (row stride ldr), C8 must be NULL;
  *   act GELU: C (M, N) f16 and C8 (M, 2N) bytes (row pitch 2 * ldc) in the A8 layout - the operand of the next projection.
- * M % 256 == 0, N % 256 == 0, K % 128 == 0. */
+ * M % 256 == 0, N % 256 == 0, K % 128 == 0, all > 0; lda, ldw % 8 == 0 and >= K; ldc % 4 == 0 and >= N; with a residual ldr % 4 == 0 and
+ * >= N; A16, A8, W16, W8, C non-NULL; GELU takes no residual.  Anything else returns hipErrorInvalidValue before a launch (this holds for
+ * the _sel and _ws forms below too). */
 int ruart_gemm_16c_nt(const void* A16, const void* A8, int lda, const void* W16, const void* W8, int ldw, const float* bias,
                       const float* residual, int ldr, void* C, int ldc, void* C8, int M, int N, int K, int act, void* stream);
 /* out4 = {SA_LO, SA_HI, SW_HI, SW_LO}: the power-of-two exponents of the e4m3 companions described above, as compiled into this library
@@ -85,19 +90,22 @@ int ruart_gemm_16c_nt_ws(const void* A16, const void* A8, int lda, const void* W
                          const float* residual, int ldr, void* C, int ldc, void* C8, int M, int N, int K, int act, int corr, void* tail_ws,
                          size_t tail_ws_bytes, int cus, void* stream);
 /* Training forward of the intermediate dense (Models/Bert/modeling.py:287-288): G16 = gelu(A . W^T + bias) and the pre-activation H16, both
- * (M x N) in the operands' 16-bit type, row stride ldc.  M, N % 256 == 0, K % 128 == 0. */
+ * (M x N) in the operands' 16-bit type, row stride ldc.  M, N % 256 == 0, K % 128 == 0, all > 0; lda, ldw % 8 == 0 and >= K; ldc % 4 == 0 and
+ * >= N; A, W, H16, G16 non-NULL; in_dtype BF16 or F16 (else hipErrorInvalidValue before a launch). */
 int ruart_gemm_16_nt_gelu2(const void* A, int lda, const void* W, int ldw, const float* bias, void* H16, void* G16, int ldc, int M, int N, int K,
                            int in_dtype, void* stream);
 /* Backward from the output dense to the intermediate dense output in one kernel: acc = dY (M x K bf16) . Wt (N x K bf16 = W2^T)^T, then with
  * the saved f16 pre-activation H (M x N, row stride ldh): dH = acc * gelu'(H) and G = gelu(H), both bf16 (row stride ldc); colpart (optional,
  * ruart_gemm_16_nt_gelu_bwd_ws_floats(M, N) floats) = column sums of the unrounded dH per 128-row strip, strip-major - sum the M / 128 strips
- * in order for the intermediate bias gradient (ruart_colsum_f32_rows).  M, N % 256 == 0, K % 128 == 0. */
+ * in order for the intermediate bias gradient (ruart_colsum_f32_rows).  M, N % 256 == 0, K % 128 == 0, all > 0; lda, ldw % 8 == 0 and >= K;
+ * ldc, ldh % 4 == 0 and >= N; every pointer but colpart non-NULL (else hipErrorInvalidValue before a launch). */
 size_t ruart_gemm_16_nt_gelu_bwd_ws_floats(int M, int N);
 int ruart_gemm_16_nt_gelu_bwd(const void* dY_bf16, int lda, const void* Wt_bf16, int ldw, const void* H16, int ldh, void* dH_bf16, void* G_bf16,
                               int ldc, float* colpart, int M, int N, int K, void* stream);
 /* Split-K form for weight gradients (dW = dY^T . X with both operands given K-contiguous, i.e. transposed: ruart_transpose16):
  * part[z] (M x N fp32, row stride ldc; slabs M * ldc floats apart) = A[:, z kchunk ...] . W[:, z kchunk ...]^T, z < ceil(K / kchunk);
- * sum the slabs with ruart_splitk_reduce.  M, N % 256 == 0, K % 128 == 0, kchunk % 128 == 0. */
+ * sum the slabs with ruart_splitk_reduce.  M, N % 256 == 0, K % 128 == 0, kchunk % 128 == 0, all > 0; lda, ldw % 8 == 0 and >= K; ldc % 4 == 0
+ * and >= N; A, W, part non-NULL (else hipErrorInvalidValue before a launch). */
 int ruart_gemm_16_nt_splitk(const void* A, int lda, const void* W, int ldw, float* part, int ldc, int M, int N, int K, int kchunk,
                             int in_dtype, void* stream);
 /* The same product straight from the layouts the backward pass holds - no transposes: part[z] (M x N fp32) = P[zT..][:, :M]^T . Q[zT..][:, :N]
@@ -350,14 +358,17 @@ int ruart_bert_forward_folded(const ruart_bert_model* m, const ruart_bert_batch*
  * A rows are pre-LayerNorm rows and the epilogue finishes rstd 2^s (A W'^T - mu c) + d (`bias` = d, wscale = 2^s); kind 3: y = A W^T +
  * bias + residual (the residual rows normalised with res_part / res_gamma / res_beta when res_part != NULL), written fp32 (C), split
  * (C16, C8) and as row partials out_part.  Partials: [M][4][2] floats, slot t = (sum, sum of squares) of the row over columns
- * 256 t .. 256 t + 255 (N <= 1024); in_np / res_np = slots in use; stat_len = the row length they cover. */
+ * 256 t .. 256 t + 255 (N <= 1024); in_np / res_np = slots in use; stat_len = the row length they cover.  Sizes and pitches as
+ * ruart_gemm_16c_nt (lda, ldw % 8 == 0 and >= K; ldc % 4 == 0 and >= N; with a residual ldr % 4 == 0 and >= N): anything else returns
+ * hipErrorInvalidValue before a launch. */
 int ruart_gemm_16c_nt_fold(const void* A16, const void* A8, int lda, const void* W16, const void* W8, int ldw, const float* bias, int kind,
                            const float* in_part, int in_np, const float* colc, float wscale, const float* residual, int ldr,
                            const float* res_part, int res_np, const float* res_gamma, const float* res_beta, void* C, int ldc, void* C16,
                            void* C8, float* out_part, int M, int N, int K, int stat_len, float eps, void* stream);
 /* The same projections for the plain 16-bit pass (dtype = F16 or BF16; round 6; Models/Bert/modeling.py:164-168 folded into :225-227,
  * 261, 287-288, 300): kind 0 / 2: C (16-bit) = [gelu] (rstd 2^s (A W'^T - mu c) + d), in_part required; kind 3: y = A W^T + bias + residual
- * (16-bit rows, normalised on the way in when res_part != NULL), C = y in 16 bits, out_part = the partials of the unrounded y. */
+ * (16-bit rows, normalised on the way in when res_part != NULL), C = y in 16 bits, out_part = the partials of the unrounded y.  M, N % 256
+ * == 0, K % 128 == 0, all > 0; pitches as ruart_gemm_16_nt (kind 3: ldr % 4 == 0 and >= N), else hipErrorInvalidValue before a launch. */
 int ruart_gemm_16_nt_fold(const void* A, int lda, const void* W, int ldw, const float* bias, int kind, const float* in_part, int in_np,
                           const float* colc, float wscale, const void* residual, int ldr, const float* res_part, int res_np,
                           const float* res_gamma, const float* res_beta, void* C, int ldc, float* out_part, int M, int N, int K, int stat_len,

@@ -1042,7 +1042,10 @@ extern "C" int ruart_gemm_16_nt_ws(const void* A, int lda, const void* W, int ld
                                    int residual_dtype, void* C, int ldc, int out_dtype, int M, int N, int K, int act, int in_dtype,
                                    void* tail_ws, size_t tail_ws_bytes, int cus, void* stream) {
   RUART_ENTRY();
-  if (M % BM || N % BN || K % BK || (lda & 7) || (ldw & 7) || (ldc & 3)) return (int)hipErrorInvalidValue;
+  // every argument check sits in front of ruart_prof_begin_: an error return never leaves a profiling event open
+  if (M <= 0 || N <= 0 || K <= 0 || M % BM || N % BN || K % BK) return (int)hipErrorInvalidValue;
+  if ((lda & 7) || (ldw & 7) || (ldc & 3) || lda < K || ldw < K || ldc < N || !A || !W || !C) return (int)hipErrorInvalidValue;
+  if (residual && ((ldr & 3) || ldr < N || act == RUART_ACT_GELU)) return (int)hipErrorInvalidValue;
   if (act != RUART_ACT_NONE && act != RUART_ACT_GELU) return (int)hipErrorInvalidValue;
   if (in_dtype != RUART_DT_BF16 && in_dtype != RUART_DT_F16) return (int)hipErrorInvalidValue;
   if (out_dtype != RUART_DT_F32 && out_dtype != in_dtype) return (int)hipErrorInvalidValue;
@@ -1083,14 +1086,14 @@ static void launch_gelu2(const void* A, int lda, const void* W, int ldw, const f
 extern "C" int ruart_gemm_16_nt_gelu2(const void* A, int lda, const void* W, int ldw, const float* bias, void* H16, void* G16, int ldc, int M,
                                       int N, int K, int in_dtype, void* stream) {
   RUART_ENTRY();
-  if (M <= 0 || M % BM4 || N % BN4 || K % 128 || (lda & 7) || (ldw & 7) || (ldc & 3) || !H16 || !G16 || !A || !W) return (int)hipErrorInvalidValue;
+  if (M <= 0 || N <= 0 || K <= 0 || M % BM4 || N % BN4 || K % 128 || (lda & 7) || (ldw & 7) || (ldc & 3) || lda < K || ldw < K || ldc < N || !H16 ||
+      !G16 || !A || !W || (in_dtype != RUART_DT_BF16 && in_dtype != RUART_DT_F16))
+    return (int)hipErrorInvalidValue;
   void* rec = ruart_prof_begin_((hipStream_t)stream, M, N, K);
   if (in_dtype == RUART_DT_BF16)
     launch_gelu2<bf16_t>(A, lda, W, ldw, bias, H16, G16, ldc, M, N, K, (hipStream_t)stream);
-  else if (in_dtype == RUART_DT_F16)
-    launch_gelu2<f16_t>(A, lda, W, ldw, bias, H16, G16, ldc, M, N, K, (hipStream_t)stream);
   else
-    return (int)hipErrorInvalidValue;
+    launch_gelu2<f16_t>(A, lda, W, ldw, bias, H16, G16, ldc, M, N, K, (hipStream_t)stream);
   ruart_prof_end_(rec, (hipStream_t)stream);
   RUART_CHECK_LAUNCH();
   return 0;
@@ -1106,8 +1109,8 @@ extern "C" size_t ruart_gemm_16_nt_gelu_bwd_ws_floats(int M, int N) { return (si
 extern "C" int ruart_gemm_16_nt_gelu_bwd(const void* dY_bf16, int lda, const void* Wt_bf16, int ldw, const void* H16, int ldh, void* dH_bf16,
                                          void* G_bf16, int ldc, float* colpart, int M, int N, int K, void* stream) {
   RUART_ENTRY();
-  if (M <= 0 || M % BM4 || N % BN4 || K % 128 || (lda & 7) || (ldw & 7) || (ldc & 3) || (ldh & 3) || !dY_bf16 || !Wt_bf16 || !H16 || !dH_bf16 ||
-      !G_bf16)
+  if (M <= 0 || N <= 0 || K <= 0 || M % BM4 || N % BN4 || K % 128 || (lda & 7) || (ldw & 7) || (ldc & 3) || (ldh & 3) || lda < K || ldw < K || ldc < N ||
+      ldh < N || !dY_bf16 || !Wt_bf16 || !H16 || !dH_bf16 || !G_bf16)
     return (int)hipErrorInvalidValue;
   constexpr int lds = 2 * 2 * BM4 * BK * 2;
   auto kern = gemm_16_nt_256p8<bf16_t, false, 0, 3>;
@@ -1144,10 +1147,12 @@ extern "C" int ruart_gemm_16_nt_fold(const void* A, int lda, const void* W, int 
                                      const float* res_gamma, const float* res_beta, void* C, int ldc, float* out_part, int M, int N, int K,
                                      int stat_len, float eps, int dtype, void* stream) {
   RUART_ENTRY();
-  if (M <= 0 || M % BM4 || N % BN4 || K % (2 * BK) || (lda & 7) || (ldw & 7) || (ldc & 3) || lda < K || ldw < K || ldc < N) return (int)hipErrorInvalidValue;
+  if (M <= 0 || N <= 0 || K <= 0 || M % BM4 || N % BN4 || K % (2 * BK) || (lda & 7) || (ldw & 7) || (ldc & 3) || lda < K || ldw < K || ldc < N)
+    return (int)hipErrorInvalidValue;
   if (!A || !W || !C || stat_len <= 0 || (dtype != RUART_DT_F16 && dtype != RUART_DT_BF16)) return (int)hipErrorInvalidValue;
   if (kind == 3) {
-    if (!residual || !out_part || N > 256 * kFoldSlots || res_np > kFoldSlots || (res_part && (!res_gamma || !res_beta || res_np <= 0)) || (ldr & 3))
+    if (!residual || !out_part || N > 256 * kFoldSlots || res_np > kFoldSlots || (res_part && (!res_gamma || !res_beta || res_np <= 0)) || (ldr & 3) ||
+        ldr < N)
       return (int)hipErrorInvalidValue;
   } else if (kind == 0 || kind == 2) {
     if (!in_part || !colc || in_np <= 0 || in_np > kFoldSlots) return (int)hipErrorInvalidValue;
@@ -1189,7 +1194,9 @@ extern "C" int ruart_gemm_16_nt_fold(const void* A, int lda, const void* W, int 
 extern "C" int ruart_gemm_16_nt_splitk(const void* A, int lda, const void* W, int ldw, float* part, int ldc, int M, int N, int K, int kchunk,
                                        int in_dtype, void* stream) {
   RUART_ENTRY();
-  if (M % BM4 || N % BN4 || K % 128 || kchunk <= 0 || kchunk % 128 || (lda & 7) || (ldw & 7) || (ldc & 3) || !part) return (int)hipErrorInvalidValue;
+  if (M <= 0 || N <= 0 || K <= 0 || M % BM4 || N % BN4 || K % 128 || kchunk <= 0 || kchunk % 128 || (lda & 7) || (ldw & 7) || (ldc & 3) || lda < K ||
+      ldw < K || ldc < N || !A || !W || !part)
+    return (int)hipErrorInvalidValue;
   if (in_dtype == RUART_DT_BF16)
     launch_splitk<bf16_t>(A, lda, W, ldw, part, ldc, M, N, K, kchunk, (hipStream_t)stream);
   else if (in_dtype == RUART_DT_F16)

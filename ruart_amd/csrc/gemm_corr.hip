@@ -41,7 +41,7 @@ typedef int i32x8_t __attribute__((ext_vector_type(8)));
 // (v_rcp + v_exp run at a quarter of the fma rate).  Measured on the FFN intermediate dense (43 008 x 3072 x 768, ablated
 // builds): 403 us per launch, 375 without the GELU, 361 without the fp8 companions, 320 without
 // both - the A-S form was 405, so the epilogue is not bound by these instructions alone.  The logistic-polynomial form of the plain
-// 16-bit epilogue (3.4e-6) would be the largest error of the whole layer here.
+// 16-bit epilogue (3.5e-6) would be the largest error of the whole layer here.
 __device__ __forceinline__ float gelu_erfc7(float x) {
   const float a = fminf(fabsf(x), 7.0710678f);
   float p = fmaf(8.470145706e-06f, a, -5.390352871e-05f);
@@ -673,8 +673,10 @@ extern "C" int ruart_gemm_16c_nt_ws(const void* A16, const void* A8, int lda, co
                                     void* tail_ws, size_t tail_ws_bytes, int cus, void* stream) {
   RUART_ENTRY();
   if (corr < 0 || corr > 3 || ((corr == 1 || corr == 2) && K % 256)) return (int)hipErrorInvalidValue;
-  if (M % CBM || N % CBN || K % 128 || (lda & 7) || (ldw & 7) || (ldc & 3) || lda < K || ldw < K) return (int)hipErrorInvalidValue;
+  if (M <= 0 || N <= 0 || K <= 0 || M % CBM || N % CBN || K % 128 || (lda & 7) || (ldw & 7) || (ldc & 3) || lda < K || ldw < K || ldc < N)
+    return (int)hipErrorInvalidValue;
   if (!A16 || !A8 || !W16 || !W8 || !C) return (int)hipErrorInvalidValue;
+  if (residual && ((ldr & 3) || ldr < N)) return (int)hipErrorInvalidValue;          // (the epilogue reads the residual 16 bytes at a time)
   if (!corr_spans_ok(M, ldc, residual ? ldr : 0)) return (int)hipErrorInvalidValue;
   // every argument check sits in front of ruart_prof_begin_: an error return never leaves a profiling event open
   if (act == RUART_ACT_GELU) {
@@ -712,8 +714,10 @@ extern "C" int ruart_gemm_16c_nt_fold(const void* A16, const void* A8, int lda, 
                                       int ldc, void* C16, void* C8, float* out_part, int M, int N, int K, int stat_len, float eps,
                                       void* stream) {
   RUART_ENTRY();
-  if (M <= 0 || M % CBM || N % CBN || K % 128 || (lda & 7) || (ldw & 7) || (ldc & 3) || lda < K || ldw < K) return (int)hipErrorInvalidValue;
+  if (M <= 0 || N <= 0 || K <= 0 || M % CBM || N % CBN || K % 128 || (lda & 7) || (ldw & 7) || (ldc & 3) || lda < K || ldw < K || ldc < N)
+    return (int)hipErrorInvalidValue;
   if (!A16 || !A8 || !W16 || !W8 || !C || stat_len <= 0) return (int)hipErrorInvalidValue;
+  if (residual && ((ldr & 3) || ldr < N)) return (int)hipErrorInvalidValue;          // (the epilogue reads the residual 16 bytes at a time)
   if (!corr_spans_ok(M, ldc, residual ? ldr : 0)) return (int)hipErrorInvalidValue;
   if (kind == 3) {
     if (!residual || !C16 || !C8 || !out_part || ldc < N || N > 256 * kFoldSlots || res_np > kFoldSlots || (res_part && (!res_gamma || !res_beta || res_np <= 0))) return (int)hipErrorInvalidValue;
