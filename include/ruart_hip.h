@@ -606,7 +606,9 @@ int ruart_gemm_x3_plan(int M, int N, int K, int a_k_contiguous /* sak == 1 */, i
  *   b_keep  (K / rows_per_scale_row, N) bytes: B(k,n) *= b_keep[k / rpm][n] ? keep_scale : 0   (needs sbn == 1) - dW = dY^T (x*mask)
  *   c_scale (M / rows_per_scale_row, N) fp32 : C(m,n) *= c_scale[m / rpm][n]                                    - dX = (dY W) * mask
  * The operand masks travel as one byte per element and are read inside the operand loads (at most one of a_keep / b_keep per call;
- * M, K < 2^20); c_scale is the mask itself and is applied in the epilogue. */
+ * the masked operand's two extents - M and K with a_keep, K and N with b_keep - must be < 2^20: the mask-row index is one multiply by
+ * a float reciprocal, exact below that; a larger one is refused with hipErrorInvalidValue); c_scale is the mask itself and is applied
+ * in the epilogue. */
 /* Epilogue: C = act(A.B + bias) [* c_scale] + residual;  act = RUART_ACT_NONE | RUART_ACT_GELU (exact erf form), residual (M, N)
  * fp32 with row stride ldr or NULL - the encoder's dense+bias(+GELU)(+residual) steps in its split-operand precision mode. */
 int ruart_gemm_x3(const float* A, long long sam, long long sak, const float* B, long long sbk, long long sbn, const float* bias,

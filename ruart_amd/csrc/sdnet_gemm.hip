@@ -610,6 +610,8 @@ int gemm_xn(const float* A, long long sam, long long sak, const float* B, long l
   const float* R = residual;
   const int rpm = rows_per_scale_row > 0 ? rows_per_scale_row : 1;
   if ((a_scale && sak != 1) || (b_scale && sbn != 1)) return (int)hipErrorInvalidValue;    // see the header
+  // a masked operand's mask-row index goes through Stager::div_rpm, exact for x < 2^20 only: A's rows are M, B's (MODE 1) are K
+  if ((a_scale && (M >= (1 << 20) || K >= (1 << 20))) || (b_scale && (N >= (1 << 20) || K >= (1 << 20)))) return (int)hipErrorInvalidValue;
   const int amode = (sak == 1) ? 0 : (sam == 1 ? 1 : -1);
   const int bmode = (sbk == 1) ? 0 : (sbn == 1 ? 1 : -1);
   if (amode < 0 || bmode < 0) return (int)hipErrorInvalidValue;        // one unit stride per operand

@@ -377,7 +377,9 @@ def mm(a, b, bias=None, mode=None, out=None, a_keep=None, b_keep=None, keep_scal
         # the fused operand masks follow the operand's natural orientation only (and one operand at a time): otherwise multiply first
         if a_keep is not None and (a.stride(1) != 1 or b_keep is not None or max(M, K) >= (1 << 20)):
             a, a_keep = _one_unit_stride(apply_keep(a, a_keep)), None
-        if b_keep is not None and (b.stride(1) != 1 or max(N, K) >= (1 << 20)):
+        # (b with a unit row stride as well - a single column, or K == 1 over one column - is passed as K-contiguous below, a layout
+        # the b_keep forms do not take: the entry point refuses it)
+        if b_keep is not None and (b.stride(1) != 1 or b.stride(0) == 1 or max(N, K) >= (1 << 20)):
             b, b_keep = _one_unit_stride(apply_keep(b, b_keep)), None
     if not use_x3:
         if a_keep is not None:
