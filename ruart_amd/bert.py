@@ -516,9 +516,6 @@ def layer_outputs(layers, n_last=None):
     return (layers - stats[:, :, 0:1]) * stats[:, :, 1:2] * g[:, None, :] + b[:, None, :]
 
 
-from .ops import _ABL_SKIP      # timing diagnostics (refused without RUART_DIAGNOSTICS=1, ops.py)
-
-
 class _PoolMix(torch.autograd.Function):
     """out[dst_row[w]] = sum_l layer_w[l] * mean(layer_l[span]) ; gradient only w.r.t. layer_w (BERT is locked,
     Models/SDNet.py:91-94)."""
@@ -534,7 +531,7 @@ class _PoolMix(torch.autograd.Function):
         W = span_start.numel()
         out = torch.zeros(n_rows, H, dtype=torch.float32, device=layers.device)
         lw = layer_w.detach().to(torch.float32).contiguous()
-        if W > 0 and "pool" not in _ABL_SKIP:          # (timing diagnostics only, see ops._ABL_SKIP: empty in every product run)
+        if W > 0:
             if ln_stats is not None:
                 lib.ruart_bert_pool_mix_ln(layers, Tp * H, H, NL, ln_stats, Tp, ln_g, ln_b, span_start, span_start_last, span_len, dst_row, lw,
                                            out, H, W, H, hip.stream_ptr())
@@ -552,7 +549,7 @@ class _PoolMix(torch.autograd.Function):
         NL, Tp, H = layers.shape
         W = span_start.numel()
         g = torch.zeros(NL, dtype=torch.float32, device=layers.device)
-        if W > 0 and "pool" not in _ABL_SKIP:
+        if W > 0:
             grad_out = grad_out.contiguous()
             partial = torch.empty(W * NL, dtype=torch.float32, device=layers.device)
             if ln_stats is not None:

@@ -4,7 +4,7 @@ normalisation step runs on the hand-written HIP kernels of libruart_hip.so (ruar
 
 Module-global dropout state mirrors Models/Layers.py:15-21 (``set_dropout_prob`` / ``set_seq_dropout``).
 """
-import os
+import sys
 
 import torch
 import torch.nn as nn
@@ -15,8 +15,11 @@ from . import ops
 
 dropout_p = 0.0
 do_seq_dropout = False
-# GetFinalScores on the fused kernel (csrc/sdnet_scorer.hip); False / RUART_FUSED_SCORER=0: the op-by-op form (A/B runs, tests)
-fused_scorer_enabled = os.environ.get("RUART_FUSED_SCORER", "1") != "0"
+sys.modules[__name__].__class__ = ops.RefusesRetiredNames       # the scorer switch that lived here is a field of ops.TrunkMode
+
+
+def __getattr__(name):
+    raise ops.retired_name_error(__name__, name)
 
 
 def set_dropout_prob(p):
@@ -310,8 +313,9 @@ class GetFinalScores(nn.Module):
         self.attn2 = BilinearSeqAttn(x_size, h_size)
 
     def forward(self, x, h0, x_mask, ES_len, mask_flag=None):
-        fusable = (x.is_cuda and ops.trunk_gemm == "x3" and x.dim() == 3 and x.size(2) % 4 == 0 and x.size(1) <= 1024
-                   and fused_scorer_enabled
+        mode = ops.trunk_mode()
+        fusable = (x.is_cuda and mode.gemm == "x3" and x.dim() == 3 and x.size(2) % 4 == 0 and x.size(1) <= 1024
+                   and mode.fused_scorer          # (off / RUART_FUSED_SCORER=0: the op-by-op form - A/B runs, tests)
                    # the fused forms model the dropout of x only as the variational (B, D) mask; without VARIATIONAL_DROPOUT the
                    # reference drops x element-wise (Layers.py:32-39, 454): those configurations take the op-by-op form below
                    and (do_seq_dropout or not self.training or dropout_p == 0))

@@ -5,12 +5,15 @@ Each Function's forward AND backward launch hand-written HIP kernels through the
 modes: the vendor library's solutions for these shapes are all stream-K kernels (Tensile ``SK3``: a fixed grid of workgroups that
 exchange partial tiles through flags in memory and spin on each other), which need every workgroup of the launch resident at the
 same time; three of them launched on three streams beside the encoder's 256-workgroup GEMMs do not get that, and the device stops
-making progress (the hang of round 1).  Only the exact-fp32 validation mode (``trunk_gemm == "fp32"``) still calls
+making progress (the hang of round 1).  Only the exact-fp32 validation mode (``use_trunk_mode(gemm="fp32")``) still calls
 torch.mm, and SDNet runs that mode on ONE stream.
 There is no CPU path: a CPU tensor raises ``hip.HipError``.
 """
+import contextlib
 import ctypes
+import dataclasses
 import os
+import sys
 
 import torch
 
@@ -18,18 +21,6 @@ from . import hip
 
 _WS = {}
 _PLAN_BYTES = {}      # (M, N, K, a K-contiguous, b K-contiguous) -> split-K workspace bytes of ruart_gemm_x3_plan
-# Timing diagnostics only (tools/r04_abl.sh, r04_abl2.sh): RUART_ABL_SKIP=lstm,x3,attn (here), pool (bert.py), trunk (sdnet.py) leaves out the launches of a kernel class - outputs are
-# zero-filled, results are WRONG - to read a class's marginal cost in the pipelined step.  Empty in every product run.
-_ABL_SKIP = frozenset(x for x in os.environ.get("RUART_ABL_SKIP", "").split(",") if x)
-_HOST_DELAY_US = float(os.environ.get("RUART_ABL_HOST_DELAY_US", 0) or 0)
-if _ABL_SKIP or _HOST_DELAY_US:
-    # a stray variable must not corrupt a real run silently: the knobs work only next to an explicit RUART_DIAGNOSTICS=1, and say so
-    if os.environ.get("RUART_DIAGNOSTICS") != "1":
-        raise RuntimeError("RUART_ABL_SKIP / RUART_ABL_HOST_DELAY_US are timing-only ablations that produce WRONG results; "
-                           "set RUART_DIAGNOSTICS=1 beside them to confirm, or unset them")
-    import sys as _sys
-    print("ruart_amd: TIMING DIAGNOSTICS ACTIVE (RUART_ABL_SKIP=%s, RUART_ABL_HOST_DELAY_US=%g): outputs of this process are wrong"
-          % (",".join(sorted(_ABL_SKIP)), _HOST_DELAY_US), file=_sys.stderr, flush=True)
 
 
 def _scratch(device, n, tag=""):
@@ -80,11 +71,7 @@ class _FusedAttention(torch.autograd.Function):
         dl = 0 if diag is None else diag.numel()
         out = torch.empty(B, L1, D3, dtype=torch.float32, device=pa.device)
         probs = torch.empty(B, L1, L2, dtype=torch.float32, device=pa.device)
-        if "attn" in _ABL_SKIP:
-            out.zero_()
-            probs.zero_()
-        else:
-            lib.ruart_attn_fwd_pscale(pa, pk, v, mask, diag, dl, int(relu), pscale, out, probs, B, L1, L2, h, D3, hip.stream_ptr())
+        lib.ruart_attn_fwd_pscale(pa, pk, v, mask, diag, dl, int(relu), pscale, out, probs, B, L1, L2, h, D3, hip.stream_ptr())
         ctx.save_for_backward(pa, pk, v, probs, diag, pscale)
         ctx.relu = int(relu)
         return out
@@ -109,13 +96,8 @@ class _FusedAttention(torch.autograd.Function):
             kdiag, dl = diag.reshape(1).expand(h).contiguous(), h
         gdiag = (torch.empty(B * ((L1 + 15) // 16), h, dtype=torch.float32, device=pa.device)
                  if (dl > 1 and ctx.needs_input_grad[4]) else None)
-        if "attn" in _ABL_SKIP:
-            for t in (ga, gk, gv, gdiag):
-                if t is not None:
-                    t.zero_()
-        else:
-            lib.ruart_attn_bwd_pscale(pa, pk, v, probs, gout, kdiag, dl, ctx.relu, pscale, ga, gk, gv, gdiag, ds, B, L1, L2, h, D3,
-                                      hip.stream_ptr())
+        lib.ruart_attn_bwd_pscale(pa, pk, v, probs, gout, kdiag, dl, ctx.relu, pscale, ga, gk, gv, gdiag, ds, B, L1, L2, h, D3,
+                                  hip.stream_ptr())
         if gdiag is None:
             return ga, gk, gv, None, None, None, None
         gd = colsum(gdiag)
@@ -308,14 +290,87 @@ def whole_layer_norm(x, eps=1e-5, group=None):
 # ---------------------------------------------------------------------------------------------------------
 # Dense projections of the trunk.  "x3": fp32 operands split into bf16 hi + lo inside the kernel, three 16-bit MFMA products
 # (ruart_gemm_x3, relative error ~2^-16 per product, ~5x the fp32-MFMA rate); "fp32": torch.mm / addmm (rocBLAS, exact fp32
-# MFMA) - the validation mode (SDNet sets it when opt['bert_precision'] == 'fp32') and the fallback for tiny products.
-trunk_gemm = "x3"
-# GEMM form of the trunk's BACKWARD products (dX = dY W, dW = dY^T X, dW_hh): "x3" (three bf16 products, fp32-class) or "x1" (one
-# bf16 product with fp32 accumulation - what mixed-precision training uses for gradients).  SDNet.forward sets it from
-# opt['ruart_trunk_grad_gemm'] (default "x3").  Forward products always use trunk_gemm.
-trunk_grad_gemm = "x3"
-# variational-dropout masks of the projections' inputs read inside the GEMM's operand loads (see _Linear)
-fuse_operand_masks = os.environ.get("RUART_FUSE_MASK", "1") != "0"
+# MFMA) - the validation mode (SDNet runs in it when opt['bert_precision'] == 'fp32') and the fallback for tiny products.
+@dataclasses.dataclass(frozen=True)
+class TrunkMode:
+    """How the trunk's ops compute.  One mode is in effect at a time (``trunk_mode()``); ``use_trunk_mode`` changes it for a scope.
+    Every autograd Function copies what its backward needs into ``ctx`` during forward: a backward never reads the mode in effect."""
+    gemm: str = "x3"                # forward products: "x3" | "fp32"
+    # BACKWARD products (dX = dY W, dW = dY^T X, dW_hh) of an "x3" forward: "x3" (three bf16 products, fp32-class) or "x1" (one bf16
+    # product with fp32 accumulation - what mixed-precision training uses for gradients); opt['ruart_trunk_grad_gemm']
+    grad_gemm: str = "x3"
+    defer_dw: bool = False          # weight gradients of _Linear in grouped launches at the end of backward (_flush_weight_grads)
+    # variational-dropout masks of the projections' inputs read inside the GEMM's operand loads (see _Linear)
+    fuse_masks: bool = os.environ.get("RUART_FUSE_MASK", "1") != "0"
+    # GetFinalScores on the fused kernel (csrc/sdnet_scorer.hip); False: the op-by-op form (A/B runs, tests)
+    fused_scorer: bool = os.environ.get("RUART_FUSED_SCORER", "1") != "0"
+
+    _VALUES = {"gemm": ("x3", "fp32"), "grad_gemm": ("x3", "x1")}       # (no annotation: not a field)
+
+    def __post_init__(self):
+        for f in dataclasses.fields(self):
+            v = getattr(self, f.name)
+            if not (v in self._VALUES[f.name] if f.name in self._VALUES else isinstance(v, bool)):
+                raise ValueError("TrunkMode.%s = %r: %s" % (f.name, v, " | ".join(map(repr, self._VALUES.get(f.name, (True, False))))))
+
+    @property
+    def backward_gemm(self):
+        """form of the backward products of a Function whose forward ran in this mode"""
+        return self.grad_gemm if self.gemm == "x3" else self.gemm
+
+    def replace(self, **changes):
+        unknown = sorted(set(changes) - {f.name for f in dataclasses.fields(self)})
+        if unknown:
+            raise ValueError("TrunkMode has no field %s" % ", ".join(unknown))
+        return dataclasses.replace(self, **changes)
+
+
+_mode = TrunkMode()         # module-level, not thread-local: autograd's backward threads must see the same default
+
+
+def trunk_mode():
+    """The TrunkMode in effect."""
+    return _mode
+
+
+@contextlib.contextmanager
+def use_trunk_mode(mode=None, **changes):
+    """Put ``mode`` - or the mode in effect with ``changes`` applied - into effect for the ``with`` body; the previous mode is back
+    afterwards, on exceptions too.  Scopes nest; they must not overlap across threads (the store is one variable)."""
+    global _mode
+    saved = _mode
+    _mode = (saved if mode is None else mode).replace(**changes)
+    try:
+        yield _mode
+    finally:
+        _mode = saved
+
+
+_RETIRED = frozenset(("trunk_gemm", "trunk_grad_gemm", "defer_weight_grads", "fuse_operand_masks", "fused_scorer_enabled"))
+
+
+def retired_name_error(module, name):
+    """The AttributeError for ``module.name``: the mode used to be these five variables of this module and of layers."""
+    if name in _RETIRED:
+        return AttributeError("%s.%s is retired: read ops.trunk_mode(), change it with ops.use_trunk_mode()" % (module, name))
+    return AttributeError("module %r has no attribute %r" % (module, name))
+
+
+class RefusesRetiredNames(type(sys)):
+    """Module type of ops and layers: assigning a retired name raises instead of creating an attribute that nothing reads.  (Reads
+    of one are answered by the modules' ``__getattr__``, which only a missing name reaches.)"""
+
+    def __setattr__(self, name, value):
+        if name in _RETIRED:
+            raise retired_name_error(self.__name__, name)
+        super().__setattr__(name, value)
+
+
+def __getattr__(name):
+    raise retired_name_error(__name__, name)
+
+
+sys.modules[__name__].__class__ = RefusesRetiredNames
 
 
 def _one_unit_stride(t):
@@ -339,7 +394,7 @@ def _span(t):
 def mm(a, b, bias=None, mode=None, out=None, a_keep=None, b_keep=None, keep_scale=1.0, c_scale=None, rpm=1, residual=None):
     """a (M,K) . b (K,N) (+ bias (N,)) (+ residual (M,N)) -> (M,N) fp32 on the split-bf16 MFMA kernel - every size, down to a
     single row: no product of a step goes to the vendor library (see the module docstring).
-    ``mode``: 'x3' | 'x1' | 'fp32' (torch.mm: the validation mode); default = the module-level ``trunk_gemm`` (autograd Functions
+    ``mode``: 'x3' | 'x1' | 'fp32' (torch.mm: the validation mode); default = ``trunk_mode().gemm`` (autograd Functions
     pass the mode of their forward).  ``out``: optional contiguous (M, N) destination.
     Variational-dropout masks fused into the product (each mask row is shared by ``rpm`` consecutive rows): ``a_keep`` (M/rpm, K) /
     ``b_keep`` (K/rpm, N) uint8 - the operand element is multiplied by ``keep_scale`` where the byte is non-zero and dropped where
@@ -347,7 +402,7 @@ def mm(a, b, bias=None, mode=None, out=None, a_keep=None, b_keep=None, keep_scal
     multiplies the output in the epilogue."""
     M, K = a.shape
     N = b.shape[1]
-    mode = mode or trunk_gemm
+    mode = mode or trunk_mode().gemm
     if mode in ("x3", "x1"):           # the product modes have no CPU path (torch.mm below is the fp32 VALIDATION mode only)
         for t in (a, b):
             if not (t.is_cuda and t.dtype == torch.float32):
@@ -417,8 +472,6 @@ def mm(a, b, bias=None, mode=None, out=None, a_keep=None, b_keep=None, keep_scal
         if not (residual.shape == (M, N) and residual.dtype == torch.float32 and residual.stride(1) == 1):
             residual = residual.contiguous()
         ldr = residual.stride(0)
-    if "x3" in _ABL_SKIP:
-        return out.zero_()
     fn(a, sam, sak, b, sbk, sbn, bias, residual, ldr, hip.ACT_NONE, out, N, M, N, K, ws, ws_bytes, a_keep, b_keep, float(keep_scale),
        c_scale, int(rpm), hip.stream_ptr())
     return out
@@ -439,12 +492,11 @@ def colsum(x):
 
 # ---- deferred weight gradients ------------------------------------------------------------------------------------------------
 # A training step has ~45 nn.Linear sites in the trunk.  Alone, each dW = dY^T X is a small output with a long reduction: 10-30 % of
-# the chip for 20-50 us plus a split-K reduction launch.  With ``defer_weight_grads`` on (SDNet sets it for training passes), the
+# the chip for 20-50 us plus a split-K reduction launch.  With ``defer_dw`` on in the mode of its forward (opt['ruart_defer_dw']), the
 # backward of ``_Linear`` only RECORDS (dY, X, W) and queues one end-of-backward callback with the autograd engine; the callback runs
 # all recorded products as ruart_gemm_x3_tn_grouped launches (one per alignment class and wave), writes / accumulates ``W.grad`` and
 # fires the parameters' post-accumulate hooks (dp.GradSync) - all still inside ``loss.backward()``, so callers see nothing new.
 # Every product is tiled, split and summed exactly as the single launch would: bitwise the same gradients.
-defer_weight_grads = False
 _deferred = []
 
 
@@ -516,14 +568,15 @@ class _Linear(torch.autograd.Function):
     With the mask's one-byte-per-element form at hand (``keep``, ``keep_scale``: layers.MaskBank) no pass of its own applies it: the
     forward reads the bytes beside x in the operand loads (a_keep), dW = dY^T (x * mask) reads them beside x again (b_keep), and
     dX = (dY W) * mask comes out of the GEMM epilogue (c_scale) - x * mask is never materialised.  Without it (a mask drawn outside the
-    bank; ``fuse_operand_masks = False`` / RUART_FUSE_MASK=0: the form of rounds 2-3) the forward multiplies once and keeps the product."""
+    bank; ``fuse_masks`` off / RUART_FUSE_MASK=0: the form of rounds 2-3) the forward multiplies once and keeps the product."""
 
     @staticmethod
     def forward(ctx, x, w, b, mask, rpm, wparts=None, keep=None, keep_scale=1.0):
         """``wparts``: [(Parameter, row0, row1), ...] when ``w`` is a concatenation of parameters along its rows (the two directions of a
         BiLSTM input projection): deferred weight gradients are then taken per part, straight into the parameters."""
-        ctx.mode = trunk_grad_gemm if trunk_gemm == "x3" else trunk_gemm       # form of the two backward products
-        fused = (mask is not None and keep is not None and fuse_operand_masks and trunk_gemm == "x3" and not defer_weight_grads
+        m = trunk_mode()
+        ctx.mode, ctx.defer_dw = m.backward_gemm, m.defer_dw       # the backward's product form and deferral are the forward's
+        fused = (mask is not None and keep is not None and m.fuse_masks and m.gemm == "x3" and not m.defer_dw
                  and x.stride(1) == 1 and x.shape[0] < (1 << 20) and x.shape[1] < (1 << 20))
         ctx.fused, ctx.keep_scale = fused, float(keep_scale)
         xm = x if (mask is None or fused) else (x.view(-1, rpm, x.shape[1]) * mask.unsqueeze(1)).view(x.shape)
@@ -543,7 +596,7 @@ class _Linear(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             wp, parts = ctx.wparam, ctx.wparts
             done = False
-            if defer_weight_grads and ctx.mode == "x3" and gy.stride(1) == 1 and not ctx.fused:
+            if ctx.defer_dw and ctx.mode == "x3" and gy.stride(1) == 1 and not ctx.fused:
                 if wp is not None:
                     done = _defer_weight_grad(gy, xm, wp)
                 elif parts and all(p.requires_grad and p.is_leaf for p, _, _ in parts):
@@ -561,7 +614,7 @@ class _AddMM(torch.autograd.Function):
     @staticmethod
     def forward(ctx, base, x, w):
         ctx.save_for_backward(x, w)
-        ctx.mode = trunk_grad_gemm if trunk_gemm == "x3" else trunk_gemm
+        ctx.mode = trunk_mode().backward_gemm
         return mm(x, w.t(), residual=base)
 
     @staticmethod
@@ -579,7 +632,7 @@ class _MatMul2D(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b):
         ctx.save_for_backward(a, b)
-        ctx.mode = trunk_grad_gemm if trunk_gemm == "x3" else trunk_gemm
+        ctx.mode = trunk_mode().backward_gemm
         return mm(a, b)
 
     @staticmethod
@@ -597,7 +650,7 @@ def matmul2d(a, b):
 
 def addmm(base, x, w):
     """base (M, N) + x (M, K) . w (N, K)^T."""
-    if trunk_gemm != "x3":             # exact-fp32 validation mode
+    if trunk_mode().gemm != "x3":             # exact-fp32 validation mode
         return torch.addmm(base, x, w.t())
     if not x.is_cuda:
         raise hip.HipError("ops.addmm: device tensors only (there is no CPU path)")
@@ -608,7 +661,7 @@ def linear(x, w, b=None, mask=None, wparts=None):
     """F.linear for fp32 device tensors of any leading shape, through ``mm``.  ``mask`` (B, K) with x (B, T, K): variational
     dropout (x * mask[:, None, :]) applied inside the op.  A mask that carries its byte form (``mask.keep`` uint8 (B, K), ``mask.keep_scale``
     = 1/(1-p): what layers.MaskBank hands out) is read inside the three products; any other mask costs one multiply in the forward."""
-    if trunk_gemm != "x3":             # exact-fp32 validation mode
+    if trunk_mode().gemm != "x3":             # exact-fp32 validation mode
         if mask is not None:
             x = x * mask.unsqueeze(1)
         return torch.nn.functional.linear(x, w, b)
@@ -737,16 +790,10 @@ class _LstmRecurrence(torch.autograd.Function):
         gates = torch.empty_like(xproj) if need else None
         cells = torch.empty_like(y) if need else None
         hprev = torch.empty_like(y) if w_hh.requires_grad else None
-        if "lstm" in _ABL_SKIP:
-            y.zero_()
-            for t in (gates, cells, hprev):
-                if t is not None:
-                    t.zero_()
-        else:
-            ws = _lstm_workspace(h, ndir, xproj.device)
-            lib.ruart_lstm_fwd(xproj, w_hh, y, gates, cells, hprev, B, T, h, ndir, ws, ws.numel() if ws is not None else 0, hip.stream_ptr())
+        ws = _lstm_workspace(h, ndir, xproj.device)
+        lib.ruart_lstm_fwd(xproj, w_hh, y, gates, cells, hprev, B, T, h, ndir, ws, ws.numel() if ws is not None else 0, hip.stream_ptr())
         ctx.ndir, ctx.h = ndir, h
-        ctx.mode = trunk_grad_gemm if trunk_gemm == "x3" else trunk_gemm
+        ctx.mode = trunk_mode().backward_gemm
         ctx.save_for_backward(w_hh, gates, cells, hprev)
         ctx.shape = y.shape
         return y
@@ -759,11 +806,8 @@ class _LstmRecurrence(torch.autograd.Function):
         B, T, _ = ctx.shape
         gy = gy.contiguous()
         gx = torch.empty_like(gates)
-        if "lstm" in _ABL_SKIP:
-            gx.zero_()
-        else:
-            ws = _lstm_workspace(h, ndir, gy.device)
-            lib.ruart_lstm_bwd(gy, w_hh, gates, cells, gx, B, T, h, ndir, ws, ws.numel() if ws is not None else 0, hip.stream_ptr())
+        ws = _lstm_workspace(h, ndir, gy.device)
+        lib.ruart_lstm_bwd(gy, w_hh, gates, cells, gx, B, T, h, ndir, ws, ws.numel() if ws is not None else 0, hip.stream_ptr())
         # grad_W_hh[d] = sum_{b,t} da[b,t,d] (x) h_prev[b,t,d]: one GEMM per direction on column slices (strided views, no copies)
         gw = None
         if ctx.needs_input_grad[1]:
@@ -818,7 +862,7 @@ def lstm_layer(x, w_ih, w_hh, b_ih, b_hh, w_ih_r=None, w_hh_r=None, b_ih_r=None,
     wparts = None
     if bidir:
         params = (w_ih, w_ih_r, b_ih, b_hh, b_ih_r, b_hh_r, w_hh, w_hh_r)
-        if trunk_gemm == "x3" and all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() for t in params):
+        if trunk_mode().gemm == "x3" and all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() for t in params):
             w, b, whh = _LstmPackParams.apply(*params)          # one launch instead of two cats, two adds and a stack
         else:
             w = torch.cat([w_ih, w_ih_r], 0)

@@ -42,8 +42,6 @@ from .layers import Attention, DeepAttention, GetFinalScores, LinearSelfAttn, RN
 if hasattr(torch.autograd.graph, "set_warn_on_accumulate_grad_stream_mismatch"):
     torch.autograd.graph.set_warn_on_accumulate_grad_stream_mismatch(False)
 
-_HOST_DELAY_US = ops._HOST_DELAY_US          # timing diagnostics only; refused without RUART_DIAGNOSTICS=1 (ops.py)
-
 _UNSUPPORTED = ("ModelParallel", "PRE_ALIGN_after_rnn", "no_DeepAttention")
 
 
@@ -343,7 +341,7 @@ class SDNet(nn.Module):
         2 measured no difference (1 189-1 201 samples/s against 1 192-1 205 on one stream) because the trunk phase was bound by the
         host's enqueue rate either way; with the loss readback one step late (trainer._readback_later) the host is ahead of the
         device and the trunk phase is as long as its kernels take - three streams shorten that."""
-        if ops.trunk_gemm != "x3":          # exact-fp32 validation mode: its projections are library GEMMs (stream-K solutions that
+        if ops.trunk_mode().gemm != "x3":   # exact-fp32 validation mode: its projections are library GEMMs (stream-K solutions that
             return False                     # need all their workgroups resident) - never beside other streams' kernels
         if not bool(self.opt.get("ruart_streams", True)):
             return False
@@ -440,18 +438,23 @@ class SDNet(nn.Module):
         if return_score:
             raise NotImplementedError("att_score output is not part of the hot path")
         opt = self.opt
-        dev = self.device
         # trunk projections: split-bf16 MFMA kernel, or the library's exact fp32 GEMM in the fp32 validation mode
         prec = self.Bert.weights.precision if "BERT" in opt else "x3"
-        ops.trunk_gemm = opt.get("ruart_trunk_gemm", "fp32" if prec == "fp32" else "x3")
-        # gradients of the trunk's projections: three bf16 products like the forward ("x1": one product - measured worth only
-        # 0.1-0.2 ms of a 20 ms step, these products are bound by their fp32 operand loads, so it stays an option)
-        ops.trunk_grad_gemm = opt.get("ruart_trunk_grad_gemm", "x3")
         # opt['ruart_defer_dw'] (off): record every projection's weight gradient and compute them in grouped launches at the end of
         # backward (ops._flush_weight_grads; bitwise the same gradients, ~80 launches fewer).  Measured SLOWER, 26.9-27.0 against
         # 25.2-25.8 ms per step on one box: the products no longer hide inside backward but land in front of the step's final sync
-        ops.defer_weight_grads = bool(self.training and torch.is_grad_enabled() and opt.get("ruart_defer_dw", os.environ.get("RUART_DEFER_DW", "0") == "1")
-                                      and not opt.get("ruart_graph_trunk", False))
+        defer_dw = bool(self.training and torch.is_grad_enabled() and opt.get("ruart_defer_dw", os.environ.get("RUART_DEFER_DW", "0") == "1")
+                        and not opt.get("ruart_graph_trunk", False))
+        # grad_gemm: gradients of the trunk's projections in three bf16 products like the forward ("x1": one product - measured worth
+        # only 0.1-0.2 ms of a 20 ms step, these products are bound by their fp32 operand loads, so it stays an option).
+        # The mode holds for this call only (the backward keeps what it needs of it, ops.TrunkMode); the caller's is back afterwards
+        with ops.use_trunk_mode(gemm=opt.get("ruart_trunk_gemm", "fp32" if prec == "fp32" else "x3"),
+                                grad_gemm=opt.get("ruart_trunk_grad_gemm", "x3"), defer_dw=defer_dw):
+            return self._forward(q_list, ocr_list, od_list)
+
+    def _forward(self, q_list, ocr_list, od_list):
+        opt = self.opt
+        dev = self.device
         bi = self.prepare(q_list, ocr_list, od_list)
         if self.training or self.drop_emb:
             L.mask_bank.begin_step(dev)
@@ -466,14 +469,6 @@ class SDNet(nn.Module):
         else:
             layers = self.Bert.layers_for(bi.packed)
         self.launch_prefetch()               # the following step's encoder pass starts now, beside this step's trunk
-        if _HOST_DELAY_US:                   # timing diagnostics only (tools/r04_hostdelay.sh): is the host's enqueue time on the step's critical path?
-            import time
-            t_end = time.perf_counter() + _HOST_DELAY_US * 1e-6
-            while time.perf_counter() < t_end:
-                pass
-        if "trunk" in ops._ABL_SKIP:          # timing diagnostics only (ops._ABL_SKIP, empty in every product run): no trunk work at all
-            Bq = q_list[opt["q_emb_initial"]].shape[0]
-            return torch.zeros(Bq, bi.ocr_mask.shape[1] + 1, device=dev) + lw.sum() * 0.0, None
         H = self.Bert.weights.hidden
         Bq, Q = q_list[opt["q_emb_initial"]].shape
         q_mask = q_list[opt["q_emb_initial"] + "_mask"].to(dev).to(torch.uint8)    # once: the attention kernels take uint8

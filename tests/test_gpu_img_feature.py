@@ -32,7 +32,7 @@ def test_projection_linear_at_the_image_feature_shape_vs_float64():
     own contraction (db: over the 72 rows of dY); the input requires no gradient and gets none; two launches are bit-equal.
     Measured worst err / bound: y 0.024, dW 0.18, db 0.002."""
     from ruart_amd import ops
-    assert ops.trunk_gemm == "x3"
+    assert ops.trunk_mode().gemm == "x3"
     M, K, N = 72, 2048, 300
     g = torch.Generator().manual_seed(72 * 7 + 300 * 3 + 2048)
     x = torch.randn(M, K, generator=g).abs()

@@ -756,7 +756,7 @@ def test_gemm_x3_all_layouts(M, N, K):
     ref = a.double() @ b.double() + bias.double()
     bound = 2.5e-5 * (a.abs().double() @ b.abs().double()) + 1e-6
     ad, bd, biasd = a.cuda(), b.cuda(), bias.cuda()
-    assert ops.trunk_gemm == "x3"
+    assert ops.trunk_mode().gemm == "x3"
     outs = []
     for a_t in (False, True):
         for b_t in (False, True):
@@ -804,7 +804,7 @@ def test_linear_x3_fused_dropout_mask(B, T, K, N):
     values and gradients as multiplying first - at the trunk's shapes (16- and 8-byte mask loads, both tile sizes, split K) and at
     an odd width (scalar loads)."""
     from ruart_amd import ops
-    assert ops.fuse_operand_masks
+    assert ops.trunk_mode().fuse_masks
     g = torch.Generator().manual_seed(4)
     x = torch.randn(B, T, K, generator=g).cuda().requires_grad_(True)
     w = (torch.randn(N, K, generator=g) * 0.05).cuda().requires_grad_(True)

@@ -184,17 +184,17 @@ def test_linear_self_attn_vs_reference(layers_golden, gemm):
     from ruart_amd import ops
     z = layers_golden
     L.set_dropout_prob(0.0)
-    ops.trunk_gemm = gemm
-    m = L.LinearSelfAttn(z["merge_x"].shape[2]).to(DEV)
-    m.linear.weight.data, m.linear.bias.data = T(z["merge_w"]).to(DEV), T(z["merge_b"]).to(DEV)
-    x = T(z["merge_x"]).to(DEV).requires_grad_()
-    mask = T(z["merge_mask"]).to(DEV)
-    _close(m(x, mask), z["merge_alpha"], 1e-6, 1e-5, "alpha")
-    y = m.merge(x, mask)
-    _close(y, z["merge_y"], 2e-6, 1e-5, "y")
-    y.backward(T(z["merge_gy"]).to(DEV))
-    _close(x.grad, z["merge_gx"], 1e-5, 1e-4, "gx")
-    _close(m.linear.weight.grad, z["merge_gw"], 1e-5, 1e-4, "gw")
+    with ops.use_trunk_mode(gemm=gemm):
+        m = L.LinearSelfAttn(z["merge_x"].shape[2]).to(DEV)
+        m.linear.weight.data, m.linear.bias.data = T(z["merge_w"]).to(DEV), T(z["merge_b"]).to(DEV)
+        x = T(z["merge_x"]).to(DEV).requires_grad_()
+        mask = T(z["merge_mask"]).to(DEV)
+        _close(m(x, mask), z["merge_alpha"], 1e-6, 1e-5, "alpha")
+        y = m.merge(x, mask)
+        _close(y, z["merge_y"], 2e-6, 1e-5, "y")
+        y.backward(T(z["merge_gy"]).to(DEV))
+        _close(x.grad, z["merge_gx"], 1e-5, 1e-4, "gx")
+        _close(m.linear.weight.grad, z["merge_gw"], 1e-5, 1e-4, "gw")
 
 
 @pytest.mark.parametrize("gemm", ["fp32", "x3"])
@@ -204,25 +204,25 @@ def test_get_final_scores_vs_reference(layers_golden, gemm):
     from ruart_amd import ops
     z = layers_golden
     L.set_dropout_prob(0.0)
-    ops.trunk_gemm = gemm
-    X, Hh = z["score_x"].shape[2], z["score_h0"].shape[1]
-    m = L.GetFinalScores(X, Hh, yesno=False, no_answer=True, useES=True).to(DEV)
-    for n_, p in m.named_parameters():
-        p.data = T(z["score_w_" + n_]).to(DEV)
-    x = T(z["score_x"]).to(DEV).requires_grad_()
-    h0 = T(z["score_h0"]).to(DEV).requires_grad_()
-    y = m(x, h0, T(z["score_mask"]).to(DEV), int(z["score_ES"]), mask_flag=True)
-    tol = 1e-6 if gemm == "fp32" else 2e-5
-    _close(y, z["score_y"], tol, 1e-5, "scores")
-    y.backward(T(z["score_gy"]).to(DEV))
-    _close(x.grad, z["score_gx"], 10 * tol, 1e-4, "gx")
-    _close(h0.grad, z["score_gh0"], 10 * tol, 1e-4, "gh0")
-    nograd = set(z["score_nograd"].tolist())
-    for n_, p in m.named_parameters():
-        if n_ in nograd:
-            assert p.grad is None, n_
-        else:
-            _close(p.grad, z["score_g_" + n_], 10 * tol, 1e-4, "g " + n_)
+    with ops.use_trunk_mode(gemm=gemm):
+        X, Hh = z["score_x"].shape[2], z["score_h0"].shape[1]
+        m = L.GetFinalScores(X, Hh, yesno=False, no_answer=True, useES=True).to(DEV)
+        for n_, p in m.named_parameters():
+            p.data = T(z["score_w_" + n_]).to(DEV)
+        x = T(z["score_x"]).to(DEV).requires_grad_()
+        h0 = T(z["score_h0"]).to(DEV).requires_grad_()
+        y = m(x, h0, T(z["score_mask"]).to(DEV), int(z["score_ES"]), mask_flag=True)
+        tol = 1e-6 if gemm == "fp32" else 2e-5
+        _close(y, z["score_y"], tol, 1e-5, "scores")
+        y.backward(T(z["score_gy"]).to(DEV))
+        _close(x.grad, z["score_gx"], 10 * tol, 1e-4, "gx")
+        _close(h0.grad, z["score_gh0"], 10 * tol, 1e-4, "gh0")
+        nograd = set(z["score_nograd"].tolist())
+        for n_, p in m.named_parameters():
+            if n_ in nograd:
+                assert p.grad is None, n_
+            else:
+                _close(p.grad, z["score_g_" + n_], 10 * tol, 1e-4, "g " + n_)
 
 
 @pytest.mark.parametrize("tag,nl,bid,ln", [("rnn_a", 2, True, True), ("rnn_b", 1, False, False)])
@@ -233,21 +233,21 @@ def test_stacked_brnn_vs_reference(layers_golden, tag, nl, bid, ln, gemm):
     from ruart_amd import ops
     z = layers_golden
     L.set_dropout_prob(0.0)
-    ops.trunk_gemm = gemm
-    x0 = z[tag + "_x"]
-    Hh = z[tag + "_w_rnns.0.weight_hh_l0"].shape[1]
-    m = L.StackedBRNN(x0.shape[2], Hh, nl, bidirectional=bid).to(DEV)
-    for n_, p in m.named_parameters():
-        p.data = T(z[tag + "_w_" + n_]).to(DEV)
-    x = T(x0).to(DEV).requires_grad_()
-    y, ys = m(x, None, return_list=True, LN=ln)
-    tol = 2e-6 if gemm == "fp32" else 5e-5
-    _close(y, z[tag + "_y"], tol, 1e-5, "y")
-    _close(ys[0], z[tag + "_y0"], tol, 1e-5, "y0")
-    (y * T(z[tag + "_gy"]).to(DEV)).sum().add((ys[0] * T(z[tag + "_gy0"]).to(DEV)).sum()).backward()
-    _close(x.grad, z[tag + "_gx"], 20 * tol, 1e-4, "gx")
-    for n_, p in m.named_parameters():
-        _close(p.grad, z[tag + "_g_" + n_], 20 * tol, 2e-4, "g " + n_)
+    with ops.use_trunk_mode(gemm=gemm):
+        x0 = z[tag + "_x"]
+        Hh = z[tag + "_w_rnns.0.weight_hh_l0"].shape[1]
+        m = L.StackedBRNN(x0.shape[2], Hh, nl, bidirectional=bid).to(DEV)
+        for n_, p in m.named_parameters():
+            p.data = T(z[tag + "_w_" + n_]).to(DEV)
+        x = T(x0).to(DEV).requires_grad_()
+        y, ys = m(x, None, return_list=True, LN=ln)
+        tol = 2e-6 if gemm == "fp32" else 5e-5
+        _close(y, z[tag + "_y"], tol, 1e-5, "y")
+        _close(ys[0], z[tag + "_y0"], tol, 1e-5, "y0")
+        (y * T(z[tag + "_gy"]).to(DEV)).sum().add((ys[0] * T(z[tag + "_gy0"]).to(DEV)).sum()).backward()
+        _close(x.grad, z[tag + "_gx"], 20 * tol, 1e-4, "gx")
+        for n_, p in m.named_parameters():
+            _close(p.grad, z[tag + "_g_" + n_], 20 * tol, 2e-4, "g " + n_)
 
 
 @pytest.mark.parametrize("gemm", ["fp32", "x3"])
@@ -258,24 +258,24 @@ def test_deep_attention_vs_reference(golden_dir, gemm):
     from ruart_amd import ops
     z = np.load(os.path.join(golden_dir, "layers_extra.npz"))
     L.set_dropout_prob(0.0)
-    ops.trunk_gemm = gemm
-    B, L1, L2, Wd, Hh, HL, per = [int(v) for v in z["deep_dims"]]
-    m = L.DeepAttention({"hidden_size": Hh, "highlvl_hidden_size": HL}, abstr_list_cnt=2, deep_att_hidden_size_per_abstr=per,
-                        correlation_func=3, word_hidden_size=Wd).to(DEV)
-    for n_, p in m.named_parameters():
-        p.data = T(z["deep_w_" + n_]).to(DEV)
-    grab = lambda name, n: [T(z["deep_%s_%d" % (name, i)]).to(DEV).requires_grad_() for i in range(n)]
-    x1w, x1a, x2w, x2a = grab("x1_word", 1), grab("x1_abstr", 2), grab("x2_word", 1), grab("x2_abstr", 3)
-    h, pre = m(x1w, x1a, x2w, x2a, T(z["deep_m1"]).to(DEV), T(z["deep_m2"]).to(DEV), return_bef_rnn=True)
-    tol = 2e-6 if gemm == "fp32" else 5e-5
-    _close(h, z["deep_h"], tol, 1e-5, "h")
-    _close(pre, z["deep_pre"], tol, 1e-5, "pre")
-    ((h * T(z["deep_gh"]).to(DEV)).sum() + (pre * T(z["deep_gpre"]).to(DEV)).sum()).backward()
-    for name, lst in (("x1_word", x1w), ("x1_abstr", x1a), ("x2_word", x2w), ("x2_abstr", x2a)):
-        for i, t in enumerate(lst):
-            _close(t.grad, z["deep_g_%s_%d" % (name, i)], 20 * tol, 1e-4, "g %s %d" % (name, i))
-    for n_, p in m.named_parameters():
-        _close(p.grad, z["deep_g_" + n_], 20 * tol, 2e-4, "g " + n_)
+    with ops.use_trunk_mode(gemm=gemm):
+        B, L1, L2, Wd, Hh, HL, per = [int(v) for v in z["deep_dims"]]
+        m = L.DeepAttention({"hidden_size": Hh, "highlvl_hidden_size": HL}, abstr_list_cnt=2, deep_att_hidden_size_per_abstr=per,
+                            correlation_func=3, word_hidden_size=Wd).to(DEV)
+        for n_, p in m.named_parameters():
+            p.data = T(z["deep_w_" + n_]).to(DEV)
+        grab = lambda name, n: [T(z["deep_%s_%d" % (name, i)]).to(DEV).requires_grad_() for i in range(n)]
+        x1w, x1a, x2w, x2a = grab("x1_word", 1), grab("x1_abstr", 2), grab("x2_word", 1), grab("x2_abstr", 3)
+        h, pre = m(x1w, x1a, x2w, x2a, T(z["deep_m1"]).to(DEV), T(z["deep_m2"]).to(DEV), return_bef_rnn=True)
+        tol = 2e-6 if gemm == "fp32" else 5e-5
+        _close(h, z["deep_h"], tol, 1e-5, "h")
+        _close(pre, z["deep_pre"], tol, 1e-5, "pre")
+        ((h * T(z["deep_gh"]).to(DEV)).sum() + (pre * T(z["deep_gpre"]).to(DEV)).sum()).backward()
+        for name, lst in (("x1_word", x1w), ("x1_abstr", x1a), ("x2_word", x2w), ("x2_abstr", x2a)):
+            for i, t in enumerate(lst):
+                _close(t.grad, z["deep_g_%s_%d" % (name, i)], 20 * tol, 1e-4, "g %s %d" % (name, i))
+        for n_, p in m.named_parameters():
+            _close(p.grad, z["deep_g_" + n_], 20 * tol, 2e-4, "g " + n_)
 
 
 @pytest.mark.parametrize("gemm", ["fp32", "x3"])
@@ -293,28 +293,28 @@ def test_prealign_vs_reference(golden_dir, gemm):
     q, ocr, od, _, _ = synth.synthetic_batch(opt, int(z["pre_B"]), seed=int(z["pre_seed"]), n_q=nq, n_ocr=nocr, n_od=nod, bert_vocab=bv, ragged=True)
     assert ocr["num_cnt"] == z["pre_ocr_num_cnt"].tolist()
     L.set_dropout_prob(0.0)
-    ops.trunk_gemm = gemm
-    pa = L.Attention(300, z["pre_w"].shape[0], correlation_func=3, do_similarity=True).to(DEV)
-    pa.scoring.linear.weight.data = T(z["pre_w"]).to(DEV)
-    host = type("Host", (), {"pre_align": pa})()                       # _prealign reads nothing else of the SDNet
-    bi = BatchIndex(q, ocr, od, opt, torch.device(DEV))
-    key_q = "fasttext" if "fasttext" in opt["q_embedding"] else "glove"
-    qe = T(z["pre_q_emb"]).to(DEV).requires_grad_()
-    q_mask = q[key_q + "_mask"].to(DEV).to(torch.uint8)
-    tol = 2e-6 if gemm == "fp32" else 5e-5
-    for tag, idx in (("ocr", bi.ocr), ("od", bi.od)):
-        emb = T(z["pre_%s_emb" % tag]).to(DEV).requires_grad_()           # (items, Lw, 300) as the reference holds it
-        flat = idx.dev["flat_word"]
-        words = emb.reshape(-1, 300)[flat]                               # the product's packed (real words, 300) layout
-        out = SDNet._prealign(host, words, idx, qe, q_mask)
-        ref = T(z["pre_%s_out" % tag]).reshape(-1, 300)[flat.cpu()]
-        _close(out, ref.numpy(), tol, 1e-5, tag + " out")
-        g = T(z["pre_g_" + tag]).reshape(-1, 300)[flat.cpu()].to(DEV)
-        (out * g).sum().backward()
-        gref = T(z["pre_g" + tag]).reshape(-1, 300)[flat.cpu()]
-        _close(emb.grad.reshape(-1, 300)[flat], gref.numpy(), 20 * tol, 1e-4, tag + " g emb")
-    _close(qe.grad, z["pre_gq"], 20 * tol, 1e-4, "g q")
-    _close(pa.scoring.linear.weight.grad, z["pre_gw"], 20 * tol, 2e-4, "g w")
+    with ops.use_trunk_mode(gemm=gemm):
+        pa = L.Attention(300, z["pre_w"].shape[0], correlation_func=3, do_similarity=True).to(DEV)
+        pa.scoring.linear.weight.data = T(z["pre_w"]).to(DEV)
+        host = type("Host", (), {"pre_align": pa})()                       # _prealign reads nothing else of the SDNet
+        bi = BatchIndex(q, ocr, od, opt, torch.device(DEV))
+        key_q = "fasttext" if "fasttext" in opt["q_embedding"] else "glove"
+        qe = T(z["pre_q_emb"]).to(DEV).requires_grad_()
+        q_mask = q[key_q + "_mask"].to(DEV).to(torch.uint8)
+        tol = 2e-6 if gemm == "fp32" else 5e-5
+        for tag, idx in (("ocr", bi.ocr), ("od", bi.od)):
+            emb = T(z["pre_%s_emb" % tag]).to(DEV).requires_grad_()           # (items, Lw, 300) as the reference holds it
+            flat = idx.dev["flat_word"]
+            words = emb.reshape(-1, 300)[flat]                               # the product's packed (real words, 300) layout
+            out = SDNet._prealign(host, words, idx, qe, q_mask)
+            ref = T(z["pre_%s_out" % tag]).reshape(-1, 300)[flat.cpu()]
+            _close(out, ref.numpy(), tol, 1e-5, tag + " out")
+            g = T(z["pre_g_" + tag]).reshape(-1, 300)[flat.cpu()].to(DEV)
+            (out * g).sum().backward()
+            gref = T(z["pre_g" + tag]).reshape(-1, 300)[flat.cpu()]
+            _close(emb.grad.reshape(-1, 300)[flat], gref.numpy(), 20 * tol, 1e-4, tag + " g emb")
+        _close(qe.grad, z["pre_gq"], 20 * tol, 1e-4, "g q")
+        _close(pa.scoring.linear.weight.grad, z["pre_gw"], 20 * tol, 2e-4, "g w")
 
 
 @pytest.mark.parametrize("variant", ["no_answer", "plain"])

@@ -910,15 +910,15 @@ def test_fused_scorer_equals_the_elementwise_form_with_variational_dropout():
     calls = []
     orig = ga._forward_fused
     ga._forward_fused = lambda *a, **k: (calls.append(1), orig(*a, **k))[1]
-    saved = (L.do_seq_dropout, L.dropout_p, L.fused_scorer_enabled, L.mask_bank, ops.trunk_gemm)
+    saved = (L.do_seq_dropout, L.dropout_p, L.mask_bank)
 
     def run(fused):
-        L.fused_scorer_enabled = fused
         L.mask_bank = L.MaskBank()                           # unfilled: every site draws its own mask from the generator
         torch.manual_seed(5)
         ga.zero_grad(set_to_none=True)
         x, h0 = x0.to(d).requires_grad_(), h00.to(d).requires_grad_()
-        probs = ga(x, h0, mask.to(d), ES, mask_flag=True)
+        with ops.use_trunk_mode(gemm="x3", fused_scorer=fused):
+            probs = ga(x, h0, mask.to(d), ES, mask_flag=True)
         (probs * gp).sum().backward()
         ops.nan_flag.check_and_clear()
         return probs.detach(), {"x": x.grad, "h0": h0.grad, **{n: p.grad.clone() for n, p in ga.named_parameters() if p.grad is not None}}
@@ -926,13 +926,12 @@ def test_fused_scorer_equals_the_elementwise_form_with_variational_dropout():
     try:
         L.set_dropout_prob(0.3)
         L.set_seq_dropout(True)
-        ops.trunk_gemm = "x3"
         p_ref, g_ref = run(False)
         assert not calls
         p_fus, g_fus = run(True)
         assert len(calls) == 1
     finally:
-        L.do_seq_dropout, L.dropout_p, L.fused_scorer_enabled, L.mask_bank, ops.trunk_gemm = saved
+        L.do_seq_dropout, L.dropout_p, L.mask_bank = saved
         ga._forward_fused = orig
     assert g_ref.keys() == g_fus.keys() and {"x", "h0", "attn.linear.weight", "attn2.linear.bias", "noanswer_linear.weight", "noanswer_w.weight",
                                              "noanswer_w.bias"} <= set(g_ref)
@@ -943,3 +942,31 @@ def test_fused_scorer_equals_the_elementwise_form_with_variational_dropout():
     assert float((p_ref[:, :-1][mask.to(d) == 0]).abs().max()) == 0.0 and float(g_ref["x"].abs().max()) > 0
     assert e_p < 2e-5
     assert e_g[worst] < 5e-5, e_g
+
+
+def test_a_models_trunk_mode_does_not_leak(golden):
+    """SDNet.forward computes in the mode its ``opt`` asks for (bert_precision 'fp32': the exact-fp32 products) at every ops.mm /
+    ops.linear call of the pass, and the mode of the caller - here the default - is in effect again when it returns."""
+    import ruart_amd.layers as L
+    from ruart_amd import ops
+    z = golden
+    net, opt = build(z, "fp32")
+    q, ocr, od, _, _ = synth.synthetic_batch(opt, int(z["B"]), seed=int(z["batch_seed"]), n_q=30, n_ocr=100, n_od=30, bert_vocab=2000, ragged=True)
+    L.set_dropout_prob(0.0)
+    net.eval()
+    before = ops.trunk_mode()
+    assert before.gemm == "x3"
+    seen = {"mm": [], "linear": []}
+    real = ops.mm, ops.linear
+    ops.mm = lambda *a, **k: (seen["mm"].append(ops.trunk_mode().gemm), real[0](*a, **k))[1]
+    ops.linear = lambda *a, **k: (seen["linear"].append(ops.trunk_mode().gemm), real[1](*a, **k))[1]
+    try:
+        with torch.no_grad():
+            net(q, ocr, od)
+    finally:
+        ops.mm, ops.linear = real
+    net.check_nan()
+    net.Bert.close()
+    # (the fp32 forms of ops.linear do not go through ops.mm: the projections are what shows that the pass ran at all)
+    assert len(seen["linear"]) > 20 and set(seen["mm"] + seen["linear"]) == {"fp32"}, seen
+    assert ops.trunk_mode() is before

@@ -344,7 +344,8 @@ def test_linear_with_a_byte_mask_at_degenerate_shapes(B, T, K, N):
     multiplies first there.  Values and all three gradients against multiply-first in float64, at 4e-5 sum |x m| |w| (twice the peak of
     the format bound, 2.0e-5 sum |a| |b|, over at most 4 products)."""
     from ruart_amd import ops
-    assert ops.fuse_operand_masks and ops.trunk_gemm == "x3" and not ops.defer_weight_grads
+    mode = ops.trunk_mode()
+    assert mode.fuse_masks and mode.gemm == "x3" and not mode.defer_dw
     g = torch.Generator().manual_seed(100 * B + 10 * K + N)
     x = torch.randn(B, T, K, generator=g).cuda().requires_grad_(True)
     w = torch.randn(N, K, generator=g).cuda().requires_grad_(True)
@@ -367,3 +368,54 @@ def test_linear_with_a_byte_mask_at_degenerate_shapes(B, T, K, N):
     for name, got, ref, bd in zip(("y", "gx", "gw", "gb"), (y.detach(), x.grad, w.grad, b.grad), (y64.detach(), x64.grad, w64.grad, b64.grad), bounds):
         err = (got.double().cpu().reshape(ref.shape) - ref).abs()
         assert bool((err <= 4e-5 * bd.reshape(ref.shape) + 1e-30).all()), (name, float(err.max()))
+
+
+def _linear_case():
+    g = torch.Generator().manual_seed(2 * 48 * 64 + 32)
+    x, w, b, gy = (torch.randn(s, generator=g).cuda() for s in ((2, 48, 64), (32, 64), (32,), (2, 48, 32)))
+    return x.requires_grad_(True), torch.nn.Parameter(w), b.requires_grad_(True), gy
+
+
+def test_linear_backward_keeps_the_product_form_of_its_forward():
+    """ops.linear under ``use_trunk_mode(grad_gemm='x1')``, its backward after the scope has ended (where the mode in effect says x3):
+    dX and dW are bit for bit the one-product forms, which differ from the three-product forms of the same operands."""
+    from ruart_amd import ops
+    x, w, b, gy = _linear_case()
+    with ops.use_trunk_mode(grad_gemm="x1"):
+        y = ops.linear(x, w, b)
+    assert ops.trunk_mode().backward_gemm == "x3"
+    y.backward(gy)
+    torch.cuda.synchronize()
+    gy2, x2, wd = gy.view(-1, 32), x.detach().view(-1, 64), w.detach()
+    want = {m: (ops.mm(gy2, wd, mode=m), ops.mm(gy2.t(), x2, mode=m)) for m in ("x1", "x3")}
+    assert not torch.equal(want["x1"][0], want["x3"][0]) and not torch.equal(want["x1"][1], want["x3"][1])
+    assert torch.equal(x.grad.view(-1, 64), want["x1"][0])
+    assert torch.equal(w.grad, want["x1"][1])
+
+
+def test_linear_backward_keeps_the_deferral_of_its_forward():
+    """``defer_dw`` is the forward's too: on around the forward only, the backward hands dW to the end-of-backward group (once) and the
+    gradient has the bits of the undeferred one; on around the backward only, nothing is deferred."""
+    from ruart_amd import ops
+    entered = []
+    real = ops._defer_weight_grad
+    ops._defer_weight_grad = lambda *a: (entered.append(1), real(*a))[1]
+    try:
+        x, w, b, gy = _linear_case()
+        ops.linear(x, w, b).backward(gy)                                   # the default: per site
+        assert not entered
+        x2, w2, b2, _ = _linear_case()
+        with ops.use_trunk_mode(defer_dw=True):
+            y = ops.linear(x2, w2, b2)
+        y.backward(gy)
+        torch.cuda.synchronize()
+        assert len(entered) == 1 and not ops._deferred
+        assert torch.equal(w2.grad, w.grad) and torch.equal(x2.grad, x.grad) and torch.equal(b2.grad, b.grad)
+        x3, w3, b3, _ = _linear_case()
+        y = ops.linear(x3, w3, b3)
+        with ops.use_trunk_mode(defer_dw=True):
+            y.backward(gy)
+        torch.cuda.synchronize()
+        assert len(entered) == 1 and torch.equal(w3.grad, w.grad)
+    finally:
+        ops._defer_weight_grad = real

@@ -148,21 +148,19 @@ def test_scorer_heads_refuse_shapes_outside_the_contract_and_the_module_falls_ba
     mask = torch.tensor([[1, 1, 1, 0]], device=DEV)
     attempts = []
     real = ops.fused_scorer_heads
-    saved = (L.fused_scorer_enabled, L.dropout_p, ops.trunk_gemm)
+    saved = L.dropout_p
     try:
         ops.fused_scorer_heads = lambda *a, **k: (attempts.append(1), real(*a, **k))[1]
         L.set_dropout_prob(0.0)
-        ops.trunk_gemm = "x3"
-        L.fused_scorer_enabled = True
-        with torch.no_grad():
+        with torch.no_grad(), ops.use_trunk_mode(gemm="x3", fused_scorer=True):
             got = ga(x, h0, mask, 2, mask_flag=True)
             assert len(attempts) == 1
-            L.fused_scorer_enabled = False
-            want = ga(x, h0, mask, 2, mask_flag=True)
+            with ops.use_trunk_mode(fused_scorer=False):
+                want = ga(x, h0, mask, 2, mask_flag=True)
             assert len(attempts) == 1
     finally:
         ops.fused_scorer_heads = real
-        L.fused_scorer_enabled, L.dropout_p, ops.trunk_gemm = saved
+        L.dropout_p = saved
     assert got.shape == (1, 3 + Ls + 1) and torch.equal(got, want)
 
 
@@ -180,17 +178,16 @@ def test_get_final_scores_yesno_vs_reference(layers_golden, k, gemm):
     from ruart_amd import ops
     calls = []
     real = ops.fused_scorer_heads
-    saved = (L.dropout_p, L.fused_scorer_enabled, ops.trunk_gemm)
+    saved = L.dropout_p
     try:
         ops.fused_scorer_heads = lambda *a, **kw: (calls.append(1), real(*a, **kw))[1]
         L.set_dropout_prob(0.0)
-        L.fused_scorer_enabled = True
-        ops.trunk_gemm = gemm
-        check_module_against_golden(layers_golden, k, DEV, 1e-6 if gemm == "fp32" else 2e-5)
+        with ops.use_trunk_mode(gemm=gemm, fused_scorer=True):
+            check_module_against_golden(layers_golden, k, DEV, 1e-6 if gemm == "fp32" else 2e-5)
         ops.nan_flag.check_and_clear()
     finally:
         ops.fused_scorer_heads = real
-        L.dropout_p, L.fused_scorer_enabled, ops.trunk_gemm = saved
+        L.dropout_p = saved
     assert len(calls) == (1 if gemm == "x3" else 0)
 
 
@@ -218,15 +215,15 @@ def test_fused_heads_equal_the_elementwise_form_with_variational_dropout(useES, 
     gp = torch.randn(B, 3 + Ls + int(no_answer), generator=g).to(DEV)
     calls = []
     real = ops.fused_scorer_heads
-    saved = (L.do_seq_dropout, L.dropout_p, L.fused_scorer_enabled, L.mask_bank, ops.trunk_gemm)
+    saved = (L.do_seq_dropout, L.dropout_p, L.mask_bank)
 
     def run(fused):
-        L.fused_scorer_enabled = fused
         L.mask_bank = L.MaskBank()                           # unfilled: every site draws its own mask from the generator
         torch.manual_seed(5)
         ga.zero_grad(set_to_none=True)
         x, h0 = x0.to(DEV).requires_grad_(), h00.to(DEV).requires_grad_()
-        probs = ga(x, h0, mask.to(DEV), ES if useES else None, mask_flag=True)
+        with ops.use_trunk_mode(gemm="x3", fused_scorer=fused):
+            probs = ga(x, h0, mask.to(DEV), ES if useES else None, mask_flag=True)
         (probs * gp).sum().backward()
         ops.nan_flag.check_and_clear()
         return probs.detach(), {"x": x.grad, "h0": h0.grad, **{n: p.grad.clone() for n, p in ga.named_parameters() if p.grad is not None}}
@@ -235,14 +232,13 @@ def test_fused_heads_equal_the_elementwise_form_with_variational_dropout(useES, 
         ops.fused_scorer_heads = lambda *a, **k: (calls.append(1), real(*a, **k))[1]
         L.set_dropout_prob(0.3)
         L.set_seq_dropout(True)
-        ops.trunk_gemm = "x3"
         p_ref, g_ref = run(False)
         assert not calls
         p_fus, g_fus = run(True)
         assert len(calls) == 1
     finally:
         ops.fused_scorer_heads = real
-        L.do_seq_dropout, L.dropout_p, L.fused_scorer_enabled, L.mask_bank, ops.trunk_gemm = saved
+        L.do_seq_dropout, L.dropout_p, L.mask_bank = saved
     expect = {"x", "h0", "attn.linear.weight", "no_linear.weight", "yes_linear.bias", "no_read_linear.weight", "no_w.weight", "yes_w.bias",
               "no_read_w.weight"} | ({"attn2.linear.bias"} if useES else set()) | ({"noanswer_linear.weight", "noanswer_w.bias"} if no_answer else set())
     assert g_ref.keys() == g_fus.keys() and expect <= set(g_ref)

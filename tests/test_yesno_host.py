@@ -63,13 +63,13 @@ def test_get_final_scores_yesno_cpu_vs_reference(layers_golden, k):
     gradient, and no gradient exactly where the reference has none (the dead GRU; attn2 without useES)."""
     import ruart_amd.layers as L
     from ruart_amd import ops
-    saved = (L.dropout_p, ops.trunk_gemm)
+    saved = L.dropout_p
     L.set_dropout_prob(0.0)
-    ops.trunk_gemm = "fp32"
     try:
-        check_module_against_golden(layers_golden, k, "cpu", 1e-6)
+        with ops.use_trunk_mode(gemm="fp32"):
+            check_module_against_golden(layers_golden, k, "cpu", 1e-6)
     finally:
-        L.dropout_p, ops.trunk_gemm = saved
+        L.dropout_p = saved
 
 
 @pytest.mark.parametrize("k", [0, 1, 2])
@@ -83,22 +83,22 @@ def test_get_final_scores_yesno_compounds_the_h0_dropout(layers_golden):
     reach the no-answer projection are a subset of those that reach the yes/no projections, scaled 4x against 2x."""
     import ruart_amd.layers as L
     from ruart_amd import ops
-    saved = (L.dropout_p, L.do_seq_dropout, ops.trunk_gemm)
+    saved = (L.dropout_p, L.do_seq_dropout)
     seen = []
     m = build_module(layers_golden, 0).train()
     real = ops.linear
     try:
         L.set_dropout_prob(0.5)
         L.set_seq_dropout(True)
-        ops.trunk_gemm = "fp32"
         ops.linear = lambda x, w, b=None, **kw: (seen.append((x.detach().clone(), w)), real(x, w, b, **kw))[1]
         torch.manual_seed(3)
         z = layers_golden
         h0 = torch.ones(3, z["c0_h0"].shape[1])
-        m(T(z["c0_x"]), h0, T(z["c0_mask"]), int(z["c0_ES"]), mask_flag=True)
+        with ops.use_trunk_mode(gemm="fp32"):
+            m(T(z["c0_x"]), h0, T(z["c0_mask"]), int(z["c0_ES"]), mask_flag=True)
     finally:
         ops.linear = real
-        L.dropout_p, L.do_seq_dropout, ops.trunk_gemm = saved
+        L.dropout_p, L.do_seq_dropout = saved
     inputs = {id(w): x for x, w in seen}
     yn = [inputs[id(l.weight)] for l in (m.no_linear, m.yes_linear, m.no_read_linear)]
     na = inputs[id(m.noanswer_linear.weight)]

@@ -15,9 +15,9 @@ def cost(f, n=2000):
 a, b = torch.randn(256, 512, device=d), torch.randn(512, 256, device=d)
 w = torch.randn(256, 512, device=d, requires_grad=True); x = torch.randn(64, 100, 512, device=d)
 print("torch.mm                 %6.1f us" % cost(lambda: torch.mm(a, b)))
-ops.trunk_gemm = "x3"
-print("ops.mm (x3)              %6.1f us" % cost(lambda: ops.mm(a, b)))
-print("ops.linear fwd (no grad) %6.1f us" % cost(lambda: ops.linear(x.detach(), w.detach())))
+with ops.use_trunk_mode(gemm="x3"):
+    print("ops.mm (x3)              %6.1f us" % cost(lambda: ops.mm(a, b)))
+    print("ops.linear fwd (no grad) %6.1f us" % cost(lambda: ops.linear(x.detach(), w.detach())))
 q, k, v = torch.randn(64, 100, 250, device=d), torch.randn(64, 40, 250, device=d), torch.randn(64, 40, 250, device=d)
 m = torch.ones(64, 40, dtype=torch.uint8, device=d)
 print("ops.fused_attention fwd  %6.1f us" % cost(lambda: ops.fused_attention(q, k, v, m)))

@@ -4,7 +4,7 @@ median of ``--calls`` single calls after ``--warmup`` ones, the three groups int
 
   * ruart_scorer_heads_fwd / _bwd at H = 4, n_front = 3 (no_read, yes, no in front; noanswer behind)
   * ruart_scorer_fwd / _bwd (one head) on the same x
-  * GetFinalScores(yesno=True), op by op (RUART_FUSED_SCORER off), forward + backward, and the same module on the fused form
+  * GetFinalScores(yesno=True), op by op (``fused_scorer`` of the trunk mode off), forward + backward, and the same module on the fused form
 
     python tools/yesno_scorer_time.py [--calls 50] [--warmup 10] > profiles/yesno_scorer.txt
 """
@@ -53,15 +53,15 @@ def main():
             prm.copy_(torch.randn(prm.shape, generator=g) / max(prm.shape[-1], 1) ** 0.5)
     ga = ga.to(d).train()
     L.set_dropout_prob(0.0)
-    ops.trunk_gemm = "x3"
     xm, h0 = x.clone().requires_grad_(), torch.randn(B, Hh, generator=g).to(d).requires_grad_()
 
     def module(fused):
         def run():
-            L.fused_scorer_enabled = fused
             ga.zero_grad(set_to_none=True)
             xm.grad = h0.grad = None
-            (ga(xm, h0, mask, ES, mask_flag=True) * gp4).sum().backward()
+            with ops.use_trunk_mode(gemm="x3", fused_scorer=fused):
+                probs = ga(xm, h0, mask, ES, mask_flag=True)
+            (probs * gp4).sum().backward()
         return run
 
     work = {
