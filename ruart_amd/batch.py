@@ -208,7 +208,8 @@ class ItemIndex:
     """Index vectors for one item group (OCR tokens or detected objects).  Host arrays; ``.dev`` holds the int64
     device copies after ``to_device``."""
 
-    def __init__(self, items, word_key, max_num):
+    def __init__(self, items, word_key, max_num, bidir=False):
+        """``bidir`` (conf key multi2one_bidir): also the schedule of multi2one's reverse direction (``_reverse_schedule``)."""
         num_cnt = np.asarray(items["num_cnt"], dtype=np.int64)
         lens = np.concatenate([np.asarray(l, dtype=np.int64) for l in items["len_cnt"]]) if len(num_cnt) else np.zeros(0, np.int64)
         if (lens < 1).any():
@@ -256,6 +257,30 @@ class ItemIndex:
         self.dev = None
         self.emb_sort = {}
         self.extra = {}                # further int64 vectors shipped with the fields (BatchIndex: the image-feature overlay rows)
+        self.bidir = bool(bidir)
+        if self.bidir:
+            self._reverse_schedule(lens, word_start, order)
+
+    def _reverse_schedule(self, lens, word_start, order):
+        """multi2one's reverse direction (Models/SDNet.py:137 with multi2one_bidir).  The collate pads every item to the fixed width Lw
+        (Utils/VQA_Dataset.py:490-497) and the LSTM ignores the mask (Models/Layers.py:156-166), so the reverse state the model keeps
+        for an item of len words (:304, :310) is the one after Lw - len steps on the PAD input followed by ONE step on the item's last
+        real word.  The pad run is scheduled like the forward run: items sorted by pad count (descending, stable), at pad step s the
+        first n_active_rev[s] of them are alive.  rev_order: the items in that order; rev_rows: packed row of each item's last real
+        word; rev_pad: its pad count - these three in the reverse order -; rev_perm: for the j-th item of the forward order
+        (``flat_slot``) its position in the reverse order."""
+        Lw, N = self.Lw, self.N
+        pad = Lw - lens
+        order_rev = np.argsort(-pad, kind="stable")
+        ps = pad[order_rev]
+        self.maxpad = int(ps[0]) if N else 0
+        self.n_active_rev = [int((ps > s).sum()) for s in range(self.maxpad)]
+        inv = np.empty(N, dtype=np.int64)
+        inv[order_rev] = np.arange(N)
+        self.extra["rev_order"] = order_rev
+        self.extra["rev_rows"] = (word_start + lens - 1)[order_rev]
+        self.extra["rev_pad"] = ps
+        self.extra["rev_perm"] = inv[order]
 
     _FIELDS = ("item_of_word", "sample_of_word", "tok_in_sample", "step_rows", "sorted_sample", "sorted_slot", "flat_word", "flat_tok",
                "flat_slot")
@@ -323,13 +348,14 @@ class BatchIndex:
 
     def __init__(self, q_list, ocr_list, od_list, opt, device=None, bert=None, pack=None, mfma_long=None):
         wk_o, wk_q = opt["ocr_emb_initial"], opt["q_emb_initial"]
-        self.ocr = ItemIndex(ocr_list, wk_o, ocr_list["position"].size(1))
+        bidir = bool(opt.get("multi2one_bidir"))       # the reverse direction's schedule is built only for a conf with the key
+        self.ocr = ItemIndex(ocr_list, wk_o, ocr_list["position"].size(1), bidir=bidir)
         # region image features (img_feature_form): the object branch is (B, img_fea_num, .) with every row live.  Overlay form: the
         # object items are encoded as ever and their last states land on rows b * img_fea_num + k of the projected features - one flat
         # index of distinct rows (``flat_img``, in multi2one's item order like flat_slot).  Pure form: the reference encodes the object
         # items and throws the result away; here they are not indexed, embedded or put into the encoder stream at all (``self.od`` None).
         self.img_form = img_feature_form(opt)
-        self.od = None if self.img_form == "pure" else ItemIndex(od_list, wk_o, od_list["position"].size(1))
+        self.od = None if self.img_form == "pure" else ItemIndex(od_list, wk_o, od_list["position"].size(1), bidir=bidir)
         if self.img_form is not None:
             n_img = int(opt["img_fea_num"])
             if self.od is not None:
@@ -375,7 +401,8 @@ class BatchIndex:
             # bit-neutral; opt['bert_dedup'] / opt['bert_last_rows'] = False switch them off)
             frozen = "LOCK_BERT" in opt and not opt.get("bert_frozen_dropout")
             dedup = frozen and bool(opt.get("bert_dedup", True)) and bool(pack)
-            self.plan = (bool(pack), bool(mfma_long), dedup) + (("no_od_group",) if self.od is None else ())
+            self.plan = (bool(pack), bool(mfma_long), dedup) + (("no_od_group",) if self.od is None else ()) \
+                + (("m2o_bidir",) if bidir else ())
             groups = [(q_list["bert"], q_list["bert_mask"]), (ocr_list["bert"], ocr_list["bert_mask"])]
             item_groups = [(q_list, wk_q), (ocr_list, wk_o)]
             if self.od is not None:

@@ -561,6 +561,22 @@ class _PoolMix(torch.autograd.Function):
         return g, None, None, None, None, None, None, None, None, None, None
 
 
+_one = {}
+
+
+def pool_last(layers, span_start, span_len, dst_row, n_rows, span_start_last=None):
+    """out[dst_row[w]] = mean(last layer[span]) - the word feature of a conf without BERT_LINEAR_COMBINE (Models/Bert/Bert.py:92-128),
+    for a frozen encoder: the pooling entry points of ``_PoolMix`` called with ONE layer, the last one's matrix (with its own statistics
+    and gamma / beta after a LayerNorm-folded pass) and the weight 1 - a one-hot mix over all layers would read every layer's rows.
+    With n_layers = 1 the entry points take their generic forms (the register-table kernel is built for twelve layers)."""
+    one = _one.get(layers.device)
+    if one is None:
+        one = _one[layers.device] = torch.ones(1, dtype=torch.float32, device=layers.device)
+    ln = getattr(layers, "_ln", None)
+    ln = (None, None, None) if ln is None else tuple(t[-1:] for t in ln)
+    return _PoolMix.apply(one, layers[-1:], span_start, span_len, dst_row, n_rows, hip.dtype_code(layers), span_start_last, *ln)
+
+
 def word_spans(packed, group, offsets, word_mask, offsets_arr=None):
     """Descriptors for pooling one group: for every (row n, word j) with word_mask[n, j] and a non-empty span
     [st, ed) (Models/Bert/Bert.py:155-165) -> packed start, length, destination row n * Lw + j.
@@ -855,14 +871,20 @@ class Bert(nn.Module):
         return packed, bert_encode(self.weights, packed)
 
     def pool_mix(self, packed, layers, group, offsets, word_mask, layer_w, offsets_arr=None):
-        """(N, Lw, H) fp32 = sum_l layer_w[l] * pooled_l  - Bert.py:149-165 + SDNet.py:573-581 in one kernel."""
+        """(N, Lw, H) fp32 = sum_l layer_w[l] * pooled_l  - Bert.py:149-165 + SDNet.py:573-581 in one kernel.  ``layer_w`` None: the
+        last layer pooled, no mix (Bert.py:92-128)."""
         s, n, d, rows = word_spans(packed, group, offsets, word_mask, offsets_arr)
         dev = self._device
         desc = torch.from_numpy(np.concatenate([s, n, d])).to(dev)
         W = len(s)
         if getattr(self, "bert_model", None) is not None:
-            from .bert_train import pool_mix
-            out = pool_mix(layer_w, layers, desc[:W], desc[W:2 * W], desc[2 * W:], rows)
+            from .bert_train import pool_mix, pool_words
+            if layer_w is None:
+                out = pool_words(layers[-1], desc[:W], desc[W:2 * W], desc[2 * W:], rows)
+            else:
+                out = pool_mix(layer_w, layers, desc[:W], desc[W:2 * W], desc[2 * W:], rows)
+        elif layer_w is None:
+            out = pool_last(layers, desc[:W], desc[W:2 * W], desc[2 * W:], rows)
         else:
             ln = getattr(layers, "_ln", None) or (None, None, None)
             out = _PoolMix.apply(layer_w, layers, desc[:W], desc[W:2 * W], desc[2 * W:], rows, hip.dtype_code(layers), None, *ln)
@@ -871,7 +893,8 @@ class Bert(nn.Module):
 
     # -- reference-compatible call: list of per-layer pooled tensors (Bert.py:56-90, 130-176) -------------
     def forward(self, x_bert, x_bert_mask, x_bert_offset, x_mask, device=None):
-        """List of ``bert_layer`` pooled tensors (N, Lw, H), as the reference returns under BERT_LINEAR_COMBINE.  Rows longer than
+        """List of ``bert_layer`` pooled tensors (N, Lw, H), as the reference returns under BERT_LINEAR_COMBINE; without that conf key
+        ONE tensor, the last layer pooled (``original_forward``, Bert.py:92-128).  Rows longer than
         512 pieces are windowed (PackedTokens); ``opt['BERT_MAX_BatchSize']`` splits the rows into chunks that are encoded one after
         the other and concatenated (Bert.py:65-85) - result-neutral, it only bounds the size of one pass."""
         bs = getattr(self, "opt", {}).get("BERT_MAX_BatchSize")
@@ -882,8 +905,12 @@ class Bert(nn.Module):
                 ed = min(st + int(bs), N)
                 off = x_bert_offset[st:ed] if x_bert_offset is not None else None
                 parts.append(self.forward(x_bert[st:ed], x_bert_mask[st:ed], off, x_mask[st:ed], device=device))
+            if not getattr(self, "linear_combine", True):
+                return torch.cat(parts, 0)
             return [torch.cat([p[i] for p in parts], 0) for i in range(len(parts[0]))]
         packed, layers = self.encode([(x_bert, x_bert_mask)])
+        if not getattr(self, "linear_combine", True):
+            return self.pool_mix(packed, layers, 0, x_bert_offset, x_mask, None)
         outs = []
         eye = torch.eye(self.weights.n_layers, device=self._device)
         for l in range(self.weights.n_layers):

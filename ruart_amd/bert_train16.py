@@ -72,6 +72,11 @@ class _Run:
             # the CPU generator is seeded identically on every data-parallel rank (trainer.py): keep the ranks' masks apart
             self.seed = (self.seed + 0x632BE5AB * torch.distributed.get_rank()) & 0x7FFFFFFF
 
+    last_only = False                # True: no layer mix - the pass's output, and the way its gradient comes in, is the last layer (_Encoder16)
+
+    def _one(self):
+        return torch.ones(1, dtype=torch.float32, device=self.dev)
+
     def _st(self):
         return hip.stream_ptr(self.dev)                             # the stream of the tensors' device, not of the current one
 
@@ -203,6 +208,8 @@ class _Run:
         lib.ruart_cast_f32_to_16(layers32, self.layers, hip.DT_F16, NL * Tp * H, 1.0, self._st())
         self.recompute = True
         self.saved, self.wT = {}, {}
+        if self.last_only:                  # no layer mix: the last layer's fp32 rows are the output (a copy: layers32 is a reused buffer)
+            return layers32[NL - 1, :T].clone()
         if layer_w is None:
             return self.layers
         self.lw = layer_w.detach().to(torch.float32).contiguous()
@@ -231,6 +238,10 @@ class _Run:
             if self.keep:
                 self.saved[l] = saved
             x16 = self.layers[l]
+        if self.last_only:                                            # the mix kernel over ONE layer, the last, with the weight 1
+            mixed = torch.empty(Tp, H, dtype=torch.float32, device=self.dev)
+            lib.ruart_mix_rows(self.layers[NL - 1:], Tp * H, H, 1, self._one(), mixed, H, Tp, H, st())
+            return mixed[:T]
         if layer_w is None:
             return self.layers                                        # frozen-encoder use: every layer output, no mix
         self.lw = layer_w.detach().to(torch.float32).contiguous()
@@ -290,9 +301,11 @@ class _Run:
         grads = {}
         G = torch.zeros(Tp, H, dtype=torch.float32, device=dev)
         G[:T] = g_mixed
-        d_lw = torch.empty(NL, dtype=torch.float32, device=dev)
-        ws = torch.empty(512 * NL, dtype=torch.float32, device=dev)
-        lib.ruart_mix_rows_bwd(self.layers, Tp * H, H, NL, G, H, d_lw, ws, Tp, H, st())
+        d_lw = None
+        if not self.last_only:
+            d_lw = torch.empty(NL, dtype=torch.float32, device=dev)
+            ws = torch.empty(512 * NL, dtype=torch.float32, device=dev)
+            lib.ruart_mix_rows_bwd(self.layers, Tp * H, H, NL, G, H, d_lw, ws, Tp, H, st())
         wmax = max(3 * H, I)
         self.xb = torch.empty(Tp * H, dtype=torch.bfloat16, device=dev)
         self.part = torch.empty(max(256, Tp // 128) * 256 * 256 + 4 * wmax * H, dtype=torch.float32, device=dev)
@@ -321,7 +334,11 @@ class _Run:
                 self.saved[l] = self._layer_fwd(l, x16, scratch)      # this layer's activations again, on the f16 kernels
             qkv, ctx, pre1, st1, mid, h16, pre2, st2, lse = self.saved[l]
             # ---- output LayerNorm (+ the layer-mix gradient of this layer's output) and the FFN
-            d_res2, d_g2, dg2, db2, dbias2 = self._ln_bwd(dX, G, self.lw[l:l + 1], pre2, st2, P[pre + "output.LayerNorm.gamma"], self.p_h,
+            if self.last_only:                       # the output gradient enters through the last layer alone, with the weight 1
+                add, add_w = (G, self._one()) if l == NL - 1 else (None, None)
+            else:
+                add, add_w = G, self.lw[l:l + 1]
+            d_res2, d_g2, dg2, db2, dbias2 = self._ln_bwd(dX, add, add_w, pre2, st2, P[pre + "output.LayerNorm.gamma"], self.p_h,
                                                           self._seed(l, 2))
             grads[pre + "output.LayerNorm.gamma"], grads[pre + "output.LayerNorm.beta"] = dg2, db2
             grads[pre + "output.dense.bias"] = dbias2
@@ -387,9 +404,11 @@ class _Run:
 class _Encoder16(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, packed, training, keep, layer_w, *params):
+        """``layer_w`` None: no layer mix, the output is the last layer (a conf without BERT_LINEAR_COMBINE)"""
         run = _Run(model, packed, training, params, keep)
+        run.last_only = layer_w is None
         ctx.run = run if keep else None
-        ctx.lw_dtype = layer_w.dtype
+        ctx.lw_dtype = None if layer_w is None else layer_w.dtype
         return run.forward(layer_w)
 
     @staticmethod
@@ -397,7 +416,7 @@ class _Encoder16(torch.autograd.Function):
         run = ctx.run
         d_lw, grads = run.backward(g_mixed.contiguous().to(torch.float32))
         ctx.run = None
-        return (None, None, None, None, d_lw.to(ctx.lw_dtype)) + tuple(grads.get(n) for n in run.m._order)
+        return (None, None, None, None, None if d_lw is None else d_lw.to(ctx.lw_dtype)) + tuple(grads.get(n) for n in run.m._order)
 
 
 class BertModelTrainable16(BertModelTrainable):
@@ -473,8 +492,9 @@ class BertModelTrainable16(BertModelTrainable):
 
     def forward_mixed(self, packed, layer_w, training=False):
         params = [self._p[n] for n in self._order]
-        keep = torch.is_grad_enabled() and (layer_w.requires_grad or any(p.requires_grad for p in params))
+        keep = torch.is_grad_enabled() and ((layer_w is not None and layer_w.requires_grad) or any(p.requires_grad for p in params))
         if not self.supports(packed) and not (not keep and self.supports_forward_only(packed, training)):
             from .bert_train import mix_layers
-            return mix_layers(layer_w, self.forward(packed, training=training))
+            layers = self.forward(packed, training=training)
+            return layers[-1] if layer_w is None else mix_layers(layer_w, layers)
         return _Encoder16.apply(self, packed, training, keep, layer_w, *params)

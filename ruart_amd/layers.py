@@ -94,14 +94,20 @@ def dropout(x, p=0, training=False):
     return F.dropout(x, p=p, training=training)
 
 
-def row_dropout(x, rows_of, n_rows, p, training):
+def row_dropout(x, rows_of, n_rows, p, training, return_mask=False):
     """seq_dropout for a PACKED (words, D) matrix: the mask is drawn per (item, feature) and gathered through
-    ``rows_of`` (item index of each word) - the same distribution the reference draws on its padded (items, Lw, D)."""
+    ``rows_of`` (item index of each word) - the same distribution the reference draws on its padded (items, Lw, D).
+    ``return_mask``: (y, the (n_rows, D) mask or None when nothing was dropped) - for a caller that puts further positions of the same
+    items under the same mask (the pad positions of a bidirectional multi2one); only the per-item form has such a mask."""
     if not training or p == 0:
-        return x
+        return (x, None) if return_mask else x
     if not do_seq_dropout:
+        if return_mask:
+            raise NotImplementedError("element-wise dropout has no per-item mask: a bidirectional multi2one trains with VARIATIONAL_DROPOUT")
         return F.dropout(x, p=p, training=True)
-    return ops.rows_scale(x, mask_bank.take(n_rows, x.size(1), p, x), rows_of)
+    mask = mask_bank.take(n_rows, x.size(1), p, x)
+    y = ops.rows_scale(x, mask, rows_of)
+    return (y, mask) if return_mask else y
 
 
 class StackedBRNN(nn.Module):
@@ -395,14 +401,16 @@ class DeepAttention(nn.Module):
 
     def __init__(self, opt, abstr_list_cnt, deep_att_hidden_size_per_abstr, correlation_func=1, word_hidden_size=None):
         super().__init__()
-        if "no_DeepAttention" in opt:
-            raise NotImplementedError("no_DeepAttention is not in the shipped configuration")
         word_hidden_size = opt["embedding_dim"] if word_hidden_size is None else word_hidden_size
         abstr_hidden_size = opt["hidden_size"] * 2
-        att_size = abstr_hidden_size * abstr_list_cnt + word_hidden_size
-        self.int_attn_list = nn.ModuleList(
-            [Attention(att_size, deep_att_hidden_size_per_abstr, correlation_func=correlation_func) for _ in range(abstr_list_cnt + 1)])
-        rnn_input_size = abstr_hidden_size * abstr_list_cnt * 2 + (opt["highlvl_hidden_size"] * 2)
+        if "no_DeepAttention" in opt:       # Layers.py:477-479: no attention levels, the RNN reads the abstraction layers alone
+            att_size = 0
+            rnn_input_size = abstr_hidden_size * abstr_list_cnt
+        else:
+            att_size = abstr_hidden_size * abstr_list_cnt + word_hidden_size
+            self.int_attn_list = nn.ModuleList(
+                [Attention(att_size, deep_att_hidden_size_per_abstr, correlation_func=correlation_func) for _ in range(abstr_list_cnt + 1)])
+            rnn_input_size = abstr_hidden_size * abstr_list_cnt * 2 + (opt["highlvl_hidden_size"] * 2)
         self.att_size = att_size
         self.rnn_input_size = rnn_input_size
         self.rnn, self.output_size = RNN_from_opt(rnn_input_size, opt["highlvl_hidden_size"], num_layers=1)
@@ -410,9 +418,14 @@ class DeepAttention(nn.Module):
 
     def forward(self, x1_word, x1_abstr, x2_word, x2_abstr, x1_mask, x2_mask, return_bef_rnn=False, return_score=False, helper=None):
         """``helper``: an otherwise idle stream; the attention levels read the same two inputs and do not depend on each other
-        (Layers.py:508-517 only concatenates their outputs), so one of them can run there beside the others."""
+        (Layers.py:508-517 only concatenates their outputs), so one of them can run there beside the others.  Under the conf key
+        ``no_DeepAttention`` (Layers.py:513-514) there are no levels: the words, the question and ``helper`` go unused."""
         if return_score:
             raise NotImplementedError("return_score is not used by SDNet.forward")
+        if "no_DeepAttention" in self.opt:
+            x1 = torch.cat(list(x1_abstr), 2)
+            x1_hiddens = self.rnn(x1, x1_mask)
+            return (x1_hiddens, x1) if return_bef_rnn else x1_hiddens
         x1_att = torch.cat(x1_word + x1_abstr, 2)
         x2_att = torch.cat(x2_word + x2_abstr[:-1], 2)
         outs = [None] * len(x2_abstr)

@@ -15,12 +15,19 @@ What is different underneath (results identical up to fp32 summation order; BERT
   * the reference's per-op ``assert isnan == 0`` device syncs are one flag check per forward.
 
 Supported configuration: the shipped conf, its simple toggles (the embedding sets, ``position_mod`` / ``pos_att_merge_mod``,
-``label_yesno``, a trained encoder), the trunk ablation ``no_Context_Self_Attention`` and region image features in the one way the
+``label_yesno``, a trained encoder), the trunk ablations ``no_Context_Self_Attention`` and ``no_DeepAttention`` (no attention levels: the
+deep-attention RNN reads the context RNN's layers alone), a conf without ``BERT_LINEAR_COMBINE`` (the word feature is the encoder's LAST
+layer pooled, Models/Bert/Bert.py:92-128: no alphaBERT / gammaBERT, no ``dropout_emb`` on the block; bert.pool_last), ``multi2one_bidir``
+together with ``no_DeepAttention`` (``_multi2one_reverse``: the reverse direction starts at the padded end of the fixed-width item
+matrix, so its state at an item's last word is a run over the item's pad positions and one step on that word; everything behind
+multi2one is 600 wide) and region image features in the one way the
 reference can run them: ``img_feature`` with ``img_fea_way replace_od``, laid under the object items (the overlay form) or, with
 ``img_feature_replace_od``, in their place (the pure form, whose encoder stream carries no object items; batch.img_feature_form).
 Refused with NotImplementedError: ``img_fea_way final_att`` (the reference builds ``get_answer`` for 3 * ques_final_size and hands it
-ques_final_size: it cannot run), ``fixed_answers`` (its ``fixed_ocr_alpha`` exists under ``final_att`` only), ``ES_using_way
-post_process`` (host index only so far), ModelParallel, PRE_ALIGN_after_rnn, no_DeepAttention and a bidirectional multi2one.
+ques_final_size: it cannot run), ``fixed_answers`` (its ``fixed_ocr_alpha`` exists under ``final_att`` only), ``multi2one_bidir`` WITH the
+deep attention (its levels project the 1100-wide item rows and the 800-wide question rows with one matrix, Models/Layers.py:227: it
+cannot run either), PRE_ALIGN_after_rnn (unpacks one tensor into two, Models/SDNet.py:332), ``ES_using_way post_process`` (host index only
+so far) and ModelParallel.
 """
 import os
 
@@ -32,7 +39,7 @@ from . import hip
 from . import layers as L
 from . import ops
 from .batch import BatchIndex, img_feature_form
-from .bert import Bert, _PoolMix, bert_encode
+from .bert import Bert, _PoolMix, bert_encode, pool_last
 from . import bert_train
 from .layers import Attention, DeepAttention, GetFinalScores, LinearSelfAttn, RNN_from_opt, dropout, row_dropout
 
@@ -42,7 +49,7 @@ from .layers import Attention, DeepAttention, GetFinalScores, LinearSelfAttn, RN
 if hasattr(torch.autograd.graph, "set_warn_on_accumulate_grad_stream_mismatch"):
     torch.autograd.graph.set_warn_on_accumulate_grad_stream_mismatch(False)
 
-_UNSUPPORTED = ("ModelParallel", "PRE_ALIGN_after_rnn", "no_DeepAttention")
+_UNSUPPORTED = ("ModelParallel", "PRE_ALIGN_after_rnn")
 
 
 def _check_img_feature(opt):
@@ -186,6 +193,8 @@ class _Trunk(nn.Module):
 
 
 class SDNet(nn.Module):
+    bert_last_only = False           # a conf without BERT_LINEAR_COMBINE: the encoder's last layer is the word feature (set in __init__)
+
     def __init__(self, opt, embedding):
         super().__init__()
         for k in _UNSUPPORTED:
@@ -194,11 +203,25 @@ class SDNet(nn.Module):
         _check_img_feature(opt)
         if "ES_ocr" in opt and opt.get("ES_using_way") == "post_process":
             raise NotImplementedError("ES_using_way post_process is outside the accelerated hot path")
-        if opt.get("multi2one_bidir"):
-            raise NotImplementedError("bidirectional multi2one is outside the accelerated hot path")
+        self.m2o_bidir = bool(opt.get("multi2one_bidir"))
+        if self.m2o_bidir and "no_DeepAttention" not in opt:
+            # Models/Layers.py:481-484, 499-511: every level of the deep attention projects the item side [600-wide multi2one output |
+            # abstraction layers] and the question side [300-wide word vectors | abstraction layers] with the SAME matrix, built for
+            # the item side's width - the reference stops in the first level with a shape error
+            raise NotImplementedError("multi2one_bidir cannot run in the reference with the deep attention (its levels project 1100-wide "
+                                      "item rows and 800-wide question rows with one matrix): it runs together with no_DeepAttention")
+        if self.m2o_bidir and "VARIATIONAL_DROPOUT" not in opt and (float(opt.get("DROPOUT", 0.0)) > 0 or float(opt.get("dropout_emb", 0.0)) > 0):
+            # element-wise dropout draws a fresh mask at every pad position: the pad run is then no constant input per item
+            raise NotImplementedError("multi2one_bidir trains with VARIATIONAL_DROPOUT (one mask per item) or without dropout")
+        if opt.get("ruart_graph_trunk", False) and self.m2o_bidir:
+            raise NotImplementedError("opt['ruart_graph_trunk'] was never run with the 600-wide trunk of multi2one_bidir")
         if opt.get("ruart_graph_trunk", False) and "no_Context_Self_Attention" in opt:
             # the captured trunk was never run in this form: refused rather than served unverified
             raise NotImplementedError("opt['ruart_graph_trunk'] serves the trunk with the context self-attention only")
+        if opt.get("ruart_graph_trunk", False) and "no_DeepAttention" in opt:
+            raise NotImplementedError("opt['ruart_graph_trunk'] was never run with no_DeepAttention")
+        if opt.get("ruart_graph_trunk", False) and "BERT" in opt and "BERT_LINEAR_COMBINE" not in opt:
+            raise NotImplementedError("opt['ruart_graph_trunk'] was never run behind last-layer BERT features (no BERT_LINEAR_COMBINE)")
         self.opt = opt
         self.vocab_dim = 300
         self.use_cuda = opt.get("cuda") is True
@@ -241,10 +264,12 @@ class SDNet(nn.Module):
             else:
                 self.Bert.unlock()           # trainable fp32 encoder, parameters named as in the reference (bert_train.py)
             bert_dim, bert_layers = (1024, 24) if "BERT_LARGE" in opt else (768, 12)
-            if "BERT_LINEAR_COMBINE" not in opt:
-                raise NotImplementedError("the hot path is BERT_LINEAR_COMBINE (all layers mixed)")
-            self.alphaBERT = nn.Parameter(torch.ones(bert_layers))
-            self.gammaBERT = nn.Parameter(torch.ones(1, 1))
+            # without BERT_LINEAR_COMBINE the word feature is the LAST layer pooled (Models/Bert/Bert.py:92-128): no mix parameters,
+            # and no dropout_emb on the block - that dropout lives inside linear_sum (SDNet.py:481-483, 582)
+            self.bert_last_only = "BERT_LINEAR_COMBINE" not in opt
+            if not self.bert_last_only:
+                self.alphaBERT = nn.Parameter(torch.ones(bert_layers))
+                self.gammaBERT = nn.Parameter(torch.ones(1, 1))
             x_in += bert_dim if "bert" in self.ocr_embedding else 0
             q_in += bert_dim if "bert" in self.q_embedding else 0
         if "PRE_ALIGN" in opt:
@@ -304,17 +329,21 @@ class SDNet(nn.Module):
     # ------------------------------------------------------------------------------------------------------
     @property
     def device(self):
-        return self.alphaBERT.device
+        return self.ques_merger.linear.weight.device
 
     def prepare(self, q_list, ocr_list, od_list):
         """Build (or fetch) the per-batch index vectors and the packed BERT stream; cached on the batch dict."""
         bi = q_list.get("_ruart_index")
+        if bi is not None and bi.ocr.bidir != self.m2o_bidir:
+            bi = None                        # prepared for a conf with the other value of multi2one_bidir: no (or a useless) reverse schedule
         if bi is None or bi.device != self.device:
             host = q_list.get("_ruart_host_index")          # built by VQA_collate(prepare_index=True) in a loader worker
             frozen = "LOCK_BERT" in self.opt and not self.opt.get("bert_frozen_dropout")
             want = (self.Bert.pack, self.Bert.weights.dtype != 0, bool(frozen and self.opt.get("bert_dedup", True) and self.Bert.pack))
             if self.img_form == "pure":          # the encoder stream without the object group (batch.BatchIndex)
                 want += ("no_od_group",)
+            if self.m2o_bidir:                   # an index prepared without the key has no reverse schedule
+                want += ("m2o_bidir",)
             if host is not None and getattr(host, "plan", None) == want:
                 bi = host.to(self.device)
             else:
@@ -370,7 +399,7 @@ class SDNet(nn.Module):
                     raw = e
                 parts.append(dropout(e, p=p_emb, training=self.drop_emb) if "dropout_emb" in self.opt else e)
         if "bert" in self.q_embedding:
-            parts.append(dropout(bert_mix, p=p_emb, training=self.drop_emb))
+            parts.append(bert_mix if self.bert_last_only else dropout(bert_mix, p=p_emb, training=self.drop_emb))
         if "pos" in self.q_embedding:
             parts.append(ops.embedding(self.pos_embedding, q_list["pos"].to(dev), srt.get(("q", "pos"))))
         if "ent" in self.q_embedding:
@@ -379,27 +408,46 @@ class SDNet(nn.Module):
 
     def _embed_items(self, items, idx, bert_mix):
         """Packed (W, D) embedding of the real words of an item group (the reference's get_embedding_from_list,
-        SDNet.py:439-493, restricted to the rows its consumers read)."""
+        SDNet.py:439-493, restricted to the rows its consumers read).
+        Returns (words, raw, pad).  ``pad`` - multi2one_bidir only, else None - is the input of the items' PAD positions, which the
+        reverse direction of multi2one runs over (_multi2one_last), as a list of its non-zero column blocks (first column, block):
+        row 0 of the word / POS / entity tables (the padded ids are 0), each word table's under the SAME per-item ``dropout_emb`` mask
+        as the item's real words - the reference draws one (items, 1, dim) mask over the padded tensor, pads included.  A block is
+        (N, dim) under a mask and (1, dim) without one.  The BERT block (masked words are skipped, Bert.py:110-114) and the
+        pre-align block (SDNet.py:529-549 fills real words only) are zero at pads and are left out."""
         dev = self.device
         d = idx.dev
         parts, raw = [], None
+        pad = [] if self.m2o_bidir else None
+        col = 0
         p_emb = self.opt.get("dropout_emb", 0.0)
         for key in ("phoc", "fasttext", "glove"):
             if key in self.ocr_embedding:
+                table = getattr(self, self._word_table(key))
                 ids = d["ids_" + key] if "ids_" + key in d else items[key].to(dev).reshape(-1)[d["flat_word"]]
-                e = ops.embedding(getattr(self, self._word_table(key)), ids, idx.emb_sort.get(key))
+                e = ops.embedding(table, ids, idx.emb_sort.get(key))
                 if key == self.opt["ocr_emb_initial"]:
                     raw = e
-                parts.append(row_dropout(e, d["item_of_word"], idx.N, p_emb, self.drop_emb) if "dropout_emb" in self.opt else e)
+                if pad is None:
+                    parts.append(row_dropout(e, d["item_of_word"], idx.N, p_emb, self.drop_emb) if "dropout_emb" in self.opt else e)
+                else:
+                    m = None
+                    if "dropout_emb" in self.opt:
+                        e, m = row_dropout(e, d["item_of_word"], idx.N, p_emb, self.drop_emb, return_mask=True)
+                    parts.append(e)
+                    pad.append((col, table.weight[0:1] if m is None else m * table.weight[0:1]))
+                col += e.size(1)
         if "bert" in self.ocr_embedding:
-            parts.append(row_dropout(bert_mix, d["item_of_word"], idx.N, p_emb, self.drop_emb))
-        if "pos" in self.ocr_embedding:
-            ids = d["ids_pos"] if "ids_pos" in d else items["pos"].to(dev).reshape(-1)[d["flat_word"]]
-            parts.append(ops.embedding(self.pos_embedding, ids, idx.emb_sort.get("pos")))
-        if "ent" in self.ocr_embedding:
-            ids = d["ids_ent"] if "ids_ent" in d else items["ent"].to(dev).reshape(-1)[d["flat_word"]]
-            parts.append(ops.embedding(self.ent_embedding, ids, idx.emb_sort.get("ent")))
-        return torch.cat(parts, -1), raw
+            parts.append(bert_mix if self.bert_last_only else row_dropout(bert_mix, d["item_of_word"], idx.N, p_emb, self.drop_emb))
+            col += bert_mix.size(1)
+        for key, table in (("pos", getattr(self, "pos_embedding", None)), ("ent", getattr(self, "ent_embedding", None))):
+            if key in self.ocr_embedding:
+                ids = d["ids_" + key] if "ids_" + key in d else items[key].to(dev).reshape(-1)[d["flat_word"]]
+                parts.append(ops.embedding(table, ids, idx.emb_sort.get(key)))
+                if pad is not None:
+                    pad.append((col, table.weight[0:1]))
+                col += table.weight.size(1)
+        return torch.cat(parts, -1), raw, pad
 
     def _prealign(self, raw_words, idx, q_raw, q_mask):
         """SDNet.py:495-551 without the loops: scatter each sample's words into one row, attend over the question's
@@ -414,24 +462,76 @@ class SDNet(nn.Module):
         att = self.pre_align(x1, q_raw, q_mask)
         return att.reshape(-1, att.shape[2]).index_select(0, flat)
 
-    def _multi2one_last(self, x_words, idx, under=None):
-        """``multi2one`` (uni-directional LSTM, SDNet.py:137, 269-271) over real words only, returning the state at
+    def _multi2one_last(self, x_words, idx, under=None, pad=None):
+        """``multi2one`` (LSTM, SDNet.py:137, 269-271) over real words only, returning the state at
         each item's last word already scattered to (B, max_num, hidden) - what SDNet.py:288-318 builds item by item.
         ``under`` (B * img_fea_num, hidden): the projected image features the object items' states are written over (the overlay
-        form, SDNet.py:280, 301-306) instead of zeros, at rows b * img_fea_num + k."""
+        form, SDNet.py:280, 301-306) instead of zeros, at rows b * img_fea_num + k.
+        ``pad`` (multi2one_bidir; _embed_items): the pad positions' input; the output is then [forward state ; reverse state]."""
         d = idx.dev
         rnn = self.multi2one.rnns[0]
+        if self.m2o_bidir and not idx.bidir:
+            raise ValueError("this batch index was prepared without multi2one_bidir: it carries no schedule for the reverse direction")
+        mask = None
         if L.dropout_p > 0:
-            x_words = row_dropout(x_words, d["item_of_word"], idx.N, L.dropout_p, self.training)
+            if self.m2o_bidir:
+                x_words, mask = row_dropout(x_words, d["item_of_word"], idx.N, L.dropout_p, self.training, return_mask=True)
+            else:
+                x_words = row_dropout(x_words, d["item_of_word"], idx.N, L.dropout_p, self.training)
         xproj = ops.linear(x_words, rnn.weight_ih_l0, rnn.bias_ih_l0 + rnn.bias_hh_l0)
         Hh = rnn.weight_hh_l0.shape[1]
         steps = torch.split(xproj.index_select(0, d["step_rows"]), idx.n_active)      # unique rows: no sort in backward
         h0 = x_words.new_zeros(idx.N, Hh)
         h, _ = L.lstm_cell_steps(steps, rnn.weight_hh_l0, idx.n_active, h0, h0)
+        if self.m2o_bidir:
+            h = torch.cat([h, self._multi2one_reverse(x_words, idx, pad, mask).index_select(0, d["rev_perm"])], 1)
+            Hh = 2 * Hh
         if under is not None:
             return under.index_copy(0, d["flat_img"], h).view(idx.B, -1, Hh)
         flat = d["flat_slot"]                                              # (distinct rows: a plain row scatter, see _prealign)
         return x_words.new_zeros(idx.B * idx.max_num, Hh).index_copy(0, flat, h).view(idx.B, idx.max_num, Hh)
+
+    def _multi2one_reverse(self, x_words, idx, pad, mask, per_item=None):
+        """The reverse direction's state at each item's last real word (N, hidden), items in the reverse schedule's order
+        (batch.ItemIndex._reverse_schedule): the state after the item's pad count of steps on its pad input, then ONE step on its last
+        real word.  ``x_words``: the packed words under multi2one's input dropout, ``mask`` that dropout's (N, D) per-item mask or None:
+        the reference's variational mask is one (N, D) mask for all Lw positions of an item (Layers.py:163-164), so the pad input
+        goes under it too.  No new mask is drawn: the pad input uses the masks the real words took from the bank, ``dropout_emb``'s in
+        _embed_items' table order and then multi2one's.
+        Only the pad input's non-zero column blocks are projected.  With no active mask every item has the same pad input: ONE row
+        is stepped ``maxpad`` times and each item picks the state after its pad count (``per_item`` True forces the general path -
+        tests).  Otherwise the pad run is stepped like the forward run, over the items sorted by pad count."""
+        d = idx.dev
+        rnn = self.multi2one.rnns[0]
+        w_ih, w_hh = rnn.weight_ih_l0_reverse, rnn.weight_hh_l0_reverse
+        bias = rnn.bias_ih_l0_reverse + rnn.bias_hh_l0_reverse
+        Hh = w_hh.shape[1]
+        N = idx.N
+        shared = mask is None and all(b.size(0) == 1 for _, b in pad) and not per_item
+        blocks = []
+        for c0, b in pad:
+            if not shared:
+                b = b.expand(N, b.size(1))
+            blocks.append(b if mask is None else b * mask[:, c0:c0 + b.size(1)])
+        w_pad = torch.cat([w_ih[:, c0:c0 + b.size(1)] for c0, b in pad], 1)
+        pproj = ops.linear(torch.cat(blocks, 1), w_pad, bias)               # (1 or N, 4 hidden)
+        if idx.maxpad == 0:
+            h = c = x_words.new_zeros(N, Hh)
+        elif shared:
+            z = x_words.new_zeros(1, Hh)
+            hs, cs, hk, ck = [z], [z], z, z
+            for k in range(idx.maxpad):                                      # state after k + 1 pad steps
+                hk, ck = L.lstm_cell_steps([pproj], w_hh, [1], hk, ck, zero_state=(k == 0))
+                hs.append(hk)
+                cs.append(ck)
+            h, c = torch.cat(hs, 0).index_select(0, d["rev_pad"]), torch.cat(cs, 0).index_select(0, d["rev_pad"])
+        else:
+            pproj = pproj.index_select(0, d["rev_order"])                     # item order -> the reverse schedule's order
+            z = x_words.new_zeros(N, Hh)
+            h, c = L.lstm_cell_steps([pproj[:n] for n in idx.n_active_rev], w_hh, idx.n_active_rev, z, z)
+        xlast = ops.linear(x_words.index_select(0, d["rev_rows"]), w_ih, bias)
+        h, _ = L.lstm_cell_steps([xlast], w_hh, [N], h, c, zero_state=False)
+        return h
 
     # ------------------------------------------------------------------------------------------------------
     def forward(self, q_list, ocr_list, od_list, return_score=False):
@@ -460,7 +560,8 @@ class SDNet(nn.Module):
             L.mask_bank.begin_step(dev)
 
         # ---- BERT: one packed pass, then pooled + mixed per group --------------------------------------------
-        lw = self._layer_weights()
+        last_only = self.bert_last_only      # no BERT_LINEAR_COMBINE: the last layer alone, no layer weights
+        lw = None if last_only else self._layer_weights()
         trainable = getattr(self.Bert, "bert_model", None) is not None
         fused_mix = trainable and getattr(self.Bert.bert_model, "fused_mix", False)
         if fused_mix:                        # 16-bit trainable encoder: the layer mix happens inside its autograd Function
@@ -482,7 +583,7 @@ class SDNet(nn.Module):
         s_q, s_od = self._side_streams(dev) if use_streams else (main, main)
 
         if trainable and not fused_mix:
-            mixed = bert_train.mix_layers(lw, layers)                         # once for the three groups
+            mixed = layers[-1] if last_only else bert_train.mix_layers(lw, layers)      # once for the three groups
         elif not trainable:
             mixed = None
 
@@ -490,14 +591,16 @@ class SDNet(nn.Module):
             s_, l_, dst, rows, s_last = bi.spans[g]
             if trainable:
                 return bert_train.pool_words(mixed, s_, l_, dst, rows, n_pieces=bi.span_pieces[g])
+            if last_only:
+                return pool_last(layers, s_, l_, dst, rows, s_last)
             ln = getattr(layers, "_ln", None) or (None, None, None)      # a LayerNorm-folded encoder pass: the kernel normalises what it reads
             return _PoolMix.apply(lw, layers, s_, l_, dst, rows, hip.dtype_code(layers), s_last, *ln)
 
         def front(items, idx, mix, under=None):
-            words, raw = self._embed_items(items, idx, mix)
+            words, raw, pad = self._embed_items(items, idx, mix)
             if "PRE_ALIGN_befor_rnn" in opt:
                 words = torch.cat([words, self._prealign(raw, idx, q_raw, q_mask)], -1)
-            return self._multi2one_last(words, idx, under)                      # (B, max_num, 300)
+            return self._multi2one_last(words, idx, under, pad)                 # (B, max_num, 300 or, multi2one_bidir, 600)
 
         img_fea = None
         if self.img_form is not None:                                           # SDNet.py:276-281

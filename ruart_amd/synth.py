@@ -116,8 +116,9 @@ def sdnet_dims(opt):
 
 
 def sdnet_param_shapes(opt):
-    """name -> shape, in the order make_sdnet_weights draws.  Always the table WITH the context self-attention: the conf key
-    ``no_Context_Self_Attention`` is applied by make_sdnet_weights to what it drew, so that it moves no other tensor."""
+    """name -> shape, in the order make_sdnet_weights draws.  Always the table WITH the context self-attention and the deep attention:
+    the conf keys ``no_Context_Self_Attention`` and ``no_DeepAttention`` are applied by make_sdnet_weights to what it drew, so that
+    they move no other tensor."""
     d = sdnet_dims(opt)
     V = int(opt["vocab_size"])
     s = {}
@@ -189,41 +190,78 @@ def sdnet_param_shapes(opt):
     return s
 
 
+def _draw(g, name, shape, opt):
+    """one tensor of the table from the generator ``g`` (float64; the kind of draw goes by the parameter's name)"""
+    if name == "alphaBERT":
+        return 1.0 + 0.5 * g.standard_normal(shape)
+    if name == "gammaBERT":
+        return np.full(shape, 0.9)
+    if name.endswith("embed.weight"):
+        a = g.standard_normal(shape)
+        a[0] = 0.0
+        return a
+    if name.endswith("scoring.diagonal"):
+        return (np.full(shape, 1.0 / math.sqrt(opt_hidden_for(name, opt))) if shape == (1, 1, 1)
+                else 1.0 + 0.2 * g.standard_normal(shape))
+    if name.endswith("embedding.weight"):
+        return g.standard_normal(shape)
+    fan = shape[-1] if len(shape) > 1 else None
+    if "rnn" in name:            # torch LSTM/GRU init: U(-1/sqrt(hidden), +)
+        hid = shape[0] // (3 if name.startswith("get_answer.rnn") else 4)
+        k = 1.0 / math.sqrt(hid)
+    elif fan is not None:
+        k = 1.0 / math.sqrt(fan)
+    else:
+        k = 0.05
+    return g.uniform(-k, k, shape)
+
+
 def make_sdnet_weights(opt, seed=1033):
     """name -> float32 array for every entry of sdnet_param_shapes(opt).  ``no_Context_Self_Attention`` (Models/SDNet.py:180-188)
     draws that table too and then drops the self-attention's tensors and keeps the first columns of the narrower
     ``high_lvl_context_rnn`` input weights (the ones that multiply deep_attn's output in either form): every other tensor is the one
-    the conf without the key gets."""
+    the conf without the key gets.  ``no_DeepAttention`` (Models/Layers.py:477-479) is applied the same way: the attention levels'
+    tensors are dropped, ``deep_attn.rnn`` keeps the first columns of its input weights (the ones that multiply the abstraction layers
+    in either form) and ``highlvl_self_att`` the columns of what is left of its input [deep_attn output | abstraction layers | words].
+    A conf without ``BERT_LINEAR_COMBINE`` draws alphaBERT and drops the two mix parameters.  ``multi2one_bidir`` draws the table of
+    the uni-directional conf first and everything it adds afterwards, in table order: the reverse direction's four tensors, and for
+    every tensor the 600-wide multi2one output widens the block that is new, appended to the uni-directional conf's tensor - which
+    stays its leading block; tensors of unchanged shape are the uni-directional conf's."""
     g = np.random.default_rng(seed + 17)
     out = {}
     no_ctx = "no_Context_Self_Attention" in opt
-    for name, shape in sdnet_param_shapes(opt).items():
-        if name == "alphaBERT":
-            a = 1.0 + 0.5 * g.standard_normal(shape)
-        elif name == "gammaBERT":
-            a = np.full(shape, 0.9)
-        elif name.endswith("embed.weight"):
-            a = g.standard_normal(shape)
-            a[0] = 0.0
-        elif name.endswith("scoring.diagonal"):
-            a = (np.full(shape, 1.0 / math.sqrt(opt_hidden_for(name, opt))) if shape == (1, 1, 1)
-                 else 1.0 + 0.2 * g.standard_normal(shape))
-        elif name.endswith("embedding.weight"):
-            a = g.standard_normal(shape)
-        else:
-            fan = shape[-1] if len(shape) > 1 else None
-            if "rnn" in name:            # torch LSTM/GRU init: U(-1/sqrt(hidden), +)
-                hid = shape[0] // (3 if name.startswith("get_answer.rnn") else 4)
-                k = 1.0 / math.sqrt(hid)
-            elif fan is not None:
-                k = 1.0 / math.sqrt(fan)
-            else:
-                k = 0.05
-            a = g.uniform(-k, k, shape)
+    no_deep = "no_DeepAttention" in opt
+    no_mix = "BERT_LINEAR_COMBINE" not in opt
+    d = sdnet_dims(opt)
+    abstr = 2 * d["h"] * d["nl"]
+    table = sdnet_param_shapes(opt)
+    bidir = bool(opt["multi2one_bidir"])
+    uni = sdnet_param_shapes(dict(opt, multi2one_bidir=False)) if bidir else table
+    drawn = {name: _draw(g, name, shape, opt) for name, shape in uni.items()}
+    if bidir:
+        for name, shape in table.items():
+            if name not in drawn:
+                drawn[name] = _draw(g, name, shape, opt)
+            elif shape != uni[name]:
+                ax = [i for i, (a_, b_) in enumerate(zip(shape, uni[name])) if a_ != b_]
+                assert len(ax) == 1 and len(shape) == len(uni[name]), (name, shape, uni[name])
+                extra = list(shape)
+                extra[ax[0]] = shape[ax[0]] - uni[name][ax[0]]
+                drawn[name] = np.concatenate([drawn[name], _draw(g, name, tuple(extra), opt)], ax[0])
+    for name, shape in table.items():
+        a = drawn[name]
+        if no_mix and name in ("alphaBERT", "gammaBERT"):
+            continue
         if no_ctx and name.startswith("highlvl_self_att."):
             continue
         if no_ctx and name.startswith("high_lvl_context_rnn.") and "weight_ih" in name:
             a = a[:, :shape[1] // 2]
+        if no_deep and name.startswith("deep_attn.int_attn_list."):
+            continue
+        if no_deep and name.startswith("deep_attn.rnn.") and "weight_ih" in name:
+            a = a[:, :abstr]
+        if no_deep and name == "highlvl_self_att.scoring.linear.weight":
+            a = np.concatenate([a[:, :2 * d["hh"] + abstr], a[:, 2 * d["hh"] + d["deep_rnn_in"]:]], 1)
         out[name] = np.ascontiguousarray(a, dtype=np.float32)
     return out
 
@@ -393,3 +431,35 @@ def synthetic_batch(opt, B, seed=7, n_q=30, n_ocr=100, n_od=None, bert_vocab=305
               "ocr_list": ["w%d" % k for k in range(ocr["num_cnt"][b] - 1)] + ["<OCR>"],
               "image_path": "synthetic/%d.jpg" % b} for b in range(B)]
     return q, ocr, od, gt, extra
+
+
+def set_item_lengths(opt, items, lengths, seed=19, bert_vocab=30522, group="ocr"):
+    """Rewrite items of one group of a ``synthetic_batch`` (in place) to the given word counts: ``lengths`` = {item row: words}, rows
+    counted over the whole batch, never a sample's trailing sentinel item.  ``synthetic_batch`` draws at most three words per item; the
+    reverse direction of a bidirectional multi2one depends on an item's distance to the padded width, so its fixtures need items of
+    one word, of the full width ``max_{ocr,od}_len`` and in between.  An item whose words outnumber the word pieces its BERT row can
+    hold gets empty piece spans for the surplus, as ``_bertify`` cuts them."""
+    g = np.random.default_rng(seed)
+    V = int(opt["vocab_size"])
+    max_len, max_bert_len = opt["max_%s_len" % group], opt["max_%s_bert_len" % group]
+    ends = np.cumsum(items["num_cnt"]) - 1                       # the sentinel rows
+    flat_len = [l for sample in items["len_cnt"] for l in sample]
+    for row, nw in sorted(lengths.items()):
+        if row in ends or not 1 <= nw <= max_len:
+            raise ValueError("item %d: a sentinel item, or %d words outside 1 .. %d" % (row, nw, max_len))
+        for key, hi in (("fasttext", V), ("pos", opt["pos_vocab_size"]), ("ent", opt["ent_vocab_size"])):
+            items[key][row] = 0
+            items[key][row, :nw] = torch.from_numpy(g.integers(5 if key == "fasttext" else 0, hi, size=nw))
+        ids, offs = _bertify(g, nw, bert_vocab, max_bert_len)
+        items["bert"][row] = 0
+        items["bert"][row, :len(ids)] = torch.tensor(ids)
+        items["bert_offsets"][row] = offs
+        flat_len[row] = nw
+    items["fasttext_mask"] = ~items["fasttext"].eq(0)
+    items["bert_mask"] = ~items["bert"].eq(0)
+    if "phoc" in items:
+        items["phoc"], items["phoc_mask"] = items["fasttext"].clone(), items["fasttext_mask"].clone()
+    it = iter(flat_len)
+    items["len_cnt"] = [[next(it) for _ in sample] for sample in items["len_cnt"]]
+    return items
+
