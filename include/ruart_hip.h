@@ -180,7 +180,12 @@ int ruart_bert_attention_split_set_heads(int heads_per_workgroup);
  * mean(layer_l[span_start[w] .. +span_len[w])).  layers = n_layers matrices [rows, H], layer_stride elements apart.
  * span_start_last (optional): the spans' first rows inside the LAST layer's matrix when ruart_bert_forward left it compacted
  * (ruart_bert_batch.last_rows); NULL = the same rows as in every other layer.
- * Rows of `out` that no word maps to are left untouched (the caller zero-fills: masked words are zeros). */
+ * Rows of `out` that no word maps to are left untouched (the caller zero-fills: masked words are zeros).
+ * Every span has span_len >= 1: the lengths live on the device, the entry points cannot see them, so callers drop empty spans
+ * (ruart_amd.bert.word_spans does; an empty word's row stays zero like a masked one's).
+ * Row pitches ldl, ldo, ldg (elements): multiples of 4 and >= H - rows are read and written in 8- and 16-byte vectors - else
+ * hipErrorInvalidValue before a launch, as for H % 4 != 0, H > 1024, n_words <= 0, n_layers outside 1..32.  The same holds for the
+ * _bwd, _ln and _ln_bwd entry points below. */
 /* forward kernel form: 1 (default) = workgroup split along the columns (no cross-wave sum) where H % 256 == 0; 0 = split along layers */
 int ruart_bert_pool_set_variant(int cols);
 int ruart_bert_pool_mix(const void* layers, long long layer_stride, int ldl, int dtype, int n_layers, const int* span_start,
@@ -376,7 +381,8 @@ int ruart_gemm_16_nt_fold(const void* A, int lda, const void* W, int ldw, const 
 /* (mu, rstd) [rows][2] from such partials */
 int ruart_rows_stats_finish(const float* part, int np, int rows, float inv_h, float eps, float* stats, void* stream);
 /* ruart_bert_pool_mix / _bwd (Models/Bert/Bert.py:149-165 + Models/SDNet.py:573-581) over the pre-LayerNorm rows of the folded pass:
- * ln_stats [n_layers][stats_stride][2], ln_gamma / ln_beta [n_layers][H] (the layers' output LayerNorm parameters); fp32, H % 256 == 0. */
+ * ln_stats [n_layers][stats_stride][2], ln_gamma / ln_beta [n_layers][H] (the layers' output LayerNorm parameters); fp32, H % 256 == 0,
+ * all three tables non-NULL; spans and row pitches as for ruart_bert_pool_mix (hipErrorInvalidValue before a launch otherwise). */
 int ruart_bert_pool_mix_ln(const float* layers_pre, long long layer_stride, int ldl, int n_layers, const float* ln_stats,
                            long long stats_stride, const float* ln_gamma, const float* ln_beta, const int* span_start,
                            const int* span_start_last, const int* span_len, const int* dst_row, const float* layer_w, float* out, int ldo,

@@ -1626,6 +1626,9 @@ extern "C" int ruart_rows_stats_finish(const float* part, int np, int rows, floa
   return 0;
 }
 
+// row pitches of the pooling entry points: every row is read / written in 8- and 16-byte vectors from column 0
+static inline bool pool_pitch_ok(int ld, int H) { return ld >= H && ld % 4 == 0; }
+
 static int g_pool_ln_reg = 1;      // 1: twelve-layer encoders take the register-table form of the pooling kernel (0: A/B runs)
 extern "C" int ruart_bert_pool_ln_set_variant(int reg_tables) {
   g_pool_ln_reg = reg_tables < 0 ? 0 : (reg_tables > 2 ? 2 : reg_tables);      // 2: the backward's register-table form too (slower, A/B runs)
@@ -1638,6 +1641,7 @@ extern "C" int ruart_bert_pool_mix_ln(const float* layers_pre, long long layer_s
   RUART_ENTRY();
   if (H % 256 || H <= 0 || H > 1024 || n_words <= 0 || n_layers > POOL_MAX_LAYERS || n_layers <= 0 || !ln_stats || !ln_gamma || !ln_beta)
     return (int)hipErrorInvalidValue;
+  if (!pool_pitch_ok(ldl, H) || !pool_pitch_ok(ldo, H)) return (int)hipErrorInvalidValue;
   const PoolLN ln{(const float2*)ln_stats, (size_t)stats_stride, ln_gamma, ln_beta};
   if (n_layers == 12 && g_pool_ln_reg)
     hipLaunchKernelGGL(pool_mix_cols_ln_reg_kernel<12>, dim3(ceil_div(n_words, RUART_POOL_LN_WPB)), dim3(H / 4), 0, (hipStream_t)stream, layers_pre,
@@ -1656,6 +1660,7 @@ extern "C" int ruart_bert_pool_mix_ln_bwd(const float* layers_pre, long long lay
   RUART_ENTRY();
   if (H % 256 || H <= 0 || H > 1024 || n_words <= 0 || n_layers > POOL_MAX_LAYERS || n_layers <= 0 || !ln_stats || !ln_gamma || !ln_beta)
     return (int)hipErrorInvalidValue;
+  if (!pool_pitch_ok(ldl, H) || !pool_pitch_ok(ldg, H)) return (int)hipErrorInvalidValue;
   const PoolLN ln{(const float2*)ln_stats, (size_t)stats_stride, ln_gamma, ln_beta};
   if (n_layers == 12 && H == 768 && g_pool_ln_reg == 2) {        // (measured slower than the one-word form: 288 against 279 us; kept for A/B runs, variant 2)
     hipLaunchKernelGGL((pool_mix_bwd_ln_reg_kernel<3, 12>), dim3(ceil_div(n_words, RUART_POOL_LN_WPB)), dim3(256), 0, (hipStream_t)stream, layers_pre,
@@ -1704,6 +1709,7 @@ extern "C" int ruart_bert_pool_mix(const void* layers, long long layer_stride, i
                                    const float* layer_w, float* out, int ldo, int n_words, int H, void* stream) {
   RUART_ENTRY();
   if (H % 4 || H < 4 || H > 1024 || n_words <= 0 || n_layers > POOL_MAX_LAYERS || n_layers <= 0) return (int)hipErrorInvalidValue;
+  if (!pool_pitch_ok(ldl, H) || !pool_pitch_ok(ldo, H)) return (int)hipErrorInvalidValue;
   if (dtype == RUART_DT_BF16)
     launch_pool<bf16_t>(layers, layer_stride, ldl, n_layers, span_start, span_start_last, span_len, dst_row, layer_w, out, ldo, n_words, H, (hipStream_t)stream);
   else if (dtype == RUART_DT_F16)
@@ -1720,6 +1726,7 @@ extern "C" int ruart_bert_pool_mix_bwd(const void* layers, long long layer_strid
                                        void* stream) {
   RUART_ENTRY();
   if (H % 4 || H < 4 || H > 1024 || n_words <= 0 || n_layers > POOL_MAX_LAYERS || n_layers <= 0) return (int)hipErrorInvalidValue;
+  if (!pool_pitch_ok(ldl, H) || !pool_pitch_ok(ldg, H)) return (int)hipErrorInvalidValue;
   if (dtype == RUART_DT_BF16)
     launch_pool_bwd<bf16_t>(layers, layer_stride, ldl, n_layers, span_start, span_start_last, span_len, dst_row, grad_out, ldg, partial_ws, n_words, H, (hipStream_t)stream);
   else if (dtype == RUART_DT_F16)
