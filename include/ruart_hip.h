@@ -580,7 +580,12 @@ int ruart_edit_distance_pairs(const int32_t* chars, int n_chars, const int32_t* 
  *                         v = beta2 v + (1 - beta2) g'^2;  p = p dec - a m / (sqrt(v) c + eps)  with {a, dec, c} = tab[3 t .. 3 t + 2], three
  *                         DEVICE floats per tensor.  torch.optim.AdamW: a = lr_t / (1 - beta1^k), c = 1 / sqrt(1 - beta2^k), dec = 1 - lr_t wd
  *                         (k: the tensor's own step count, this step included); BertAdam (Models/Bert/optimization.py:129-152, no bias
- *                         correction): a = lr_t, c = 1, dec = 1 - lr_t wd.
+ *                         correction): a = lr_t, c = 1, dec = 1 - lr_t wd.  torch.optim.Adam without weight decay (the 'ADAM2' conf):
+ *                         a = lr / (1 - beta1^k), dec = 1, c = 1 / sqrt(1 - beta2^k).
+ *   ruart_adamax_l2_step: ruart_adamax_step with coupled L2 decay taken after the clip (the 'ADAM' conf: clip_grad_norm_ followed by
+ *                         torch.optim.Adamax(weight_decay=)):  g' = g * norm_coef[1] + weight_decay * p, then the same rule on g'.
+ *   ruart_sgd_step:       the 'SGD' conf, plain torch.optim.SGD:  p -= lr * (g * norm_coef[1])  (norm_coef NULL: no clipping); no state tensors.
+ * Every step entry returns hipErrorInvalidValue for n_chunks <= 0 or a NULL table.
  * The update's chunk list may leave out elements (embedding rows the trainer re-pins every step): they are not touched. */
 int ruart_grad_norm_clip(const float* const* grads, const int* c_tensor, const int* c_start, const int* c_count, int n_chunks,
                          float max_norm, float* partial, float* norm_coef, const float* extra_sq, void* stream);
@@ -590,6 +595,11 @@ int ruart_adamax_step(float* const* params, const float* const* grads, float* co
 int ruart_adam_step(float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq, const int* c_tensor,
                     const int* c_start, const int* c_count, int n_chunks, const float* norm_coef, const float* tab, float beta1,
                     float beta2, float eps, void* stream);
+int ruart_adamax_l2_step(float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_inf, const int* c_tensor,
+                         const int* c_start, const int* c_count, int n_chunks, const float* norm_coef, const float* clr, float beta1,
+                         float beta2, float eps, float weight_decay, void* stream);
+int ruart_sgd_step(float* const* params, const float* const* grads, const int* c_tensor, const int* c_start, const int* c_count,
+                   int n_chunks, const float* norm_coef, float lr, void* stream);
 
 /* NaN contract of the reference (assert torch.sum(torch.isnan(x)) == 0, Layers.py:169,290,430,462,467): after this
  * call every SDNet kernel ORs 1 into *flag (a device int) when it writes a NaN; the Python layer checks and clears it

@@ -7,6 +7,8 @@
 // (tensor index, start, count), one workgroup per chunk.  All sums run in a fixed order: deterministic.
 // A trained encoder may step as a group of its own (opt['bert_optimizer']): one more launch, ruart_adam_step, over its chunks, under the
 // same device-resident clip coefficient (the norm runs once over the gradients of both groups).
+// The reference's other optimizer confs step the same way: 'ADAM' (Adamax with coupled L2 decay) on ruart_adamax_l2_step, 'SGD' on
+// ruart_sgd_step, 'ADAM2' (torch.optim.Adam) on ruart_adam_step with dec = 1.
 #include "common.h"
 #include "ruart_hip.h"
 
@@ -87,6 +89,69 @@ __global__ __launch_bounds__(256) void adamax_update_kernel(float* const* __rest
   }
 }
 
+// torch.optim.Adamax(weight_decay=wd) behind clip_grad_norm_ (the reference's 'ADAM' conf): the decay is coupled, taken from the
+// parameter AFTER the clip,  g' = g coef + wd p;  then the rule above on g'.
+__global__ __launch_bounds__(256) void adamax_l2_update_kernel(float* const* __restrict__ params, const float* const* __restrict__ grads,
+                                                               float* const* __restrict__ exp_avg, float* const* __restrict__ exp_inf,
+                                                               const int* __restrict__ c_tensor, const int* __restrict__ c_start,
+                                                               const int* __restrict__ c_count, const float* __restrict__ coef_ptr,
+                                                               const float* __restrict__ clr_t, float one_minus_b1, float b2, float eps,
+                                                               float wd) {
+  const int c = blockIdx.x, t = c_tensor[c], s0 = c_start[c], n = c_count[c];
+  const float coef = coef_ptr ? coef_ptr[1] : 1.0f;
+  const float clr = clr_t[t];
+  float* p = params[t] + s0;
+  const float* g = grads[t] + s0;
+  float* m = exp_avg[t] + s0;
+  float* u = exp_inf[t] + s0;
+  for (int i = threadIdx.x * 4; i < n; i += 1024) {
+    if (i + 3 < n) {
+      f32x4_t pv = *reinterpret_cast<f32x4_t*>(p + i), mv = *reinterpret_cast<f32x4_t*>(m + i), uv = *reinterpret_cast<f32x4_t*>(u + i);
+      const f32x4_t gv = *reinterpret_cast<const f32x4_t*>(g + i);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float gr = gv[r] * coef + wd * pv[r];
+        mv[r] = mv[r] + one_minus_b1 * (gr - mv[r]);
+        uv[r] = fmaxf(uv[r] * b2, fabsf(gr) + eps);
+        pv[r] = pv[r] - clr * (mv[r] / uv[r]);
+      }
+      *reinterpret_cast<f32x4_t*>(p + i) = pv;
+      *reinterpret_cast<f32x4_t*>(m + i) = mv;
+      *reinterpret_cast<f32x4_t*>(u + i) = uv;
+    } else {
+      for (int j = i; j < n; ++j) {
+        const float gr = g[j] * coef + wd * p[j];
+        const float mj = m[j] + one_minus_b1 * (gr - m[j]);
+        const float uj = fmaxf(u[j] * b2, fabsf(gr) + eps);
+        m[j] = mj;
+        u[j] = uj;
+        p[j] = p[j] - clr * (mj / uj);
+      }
+    }
+  }
+}
+
+// torch.optim.SGD (no momentum, no decay) behind clip_grad_norm_:  p -= lr (g coef).  No state tensors.
+__global__ __launch_bounds__(256) void sgd_update_kernel(float* const* __restrict__ params, const float* const* __restrict__ grads,
+                                                         const int* __restrict__ c_tensor, const int* __restrict__ c_start,
+                                                         const int* __restrict__ c_count, const float* __restrict__ coef_ptr, float lr) {
+  const int c = blockIdx.x, t = c_tensor[c], s0 = c_start[c], n = c_count[c];
+  const float coef = coef_ptr ? coef_ptr[1] : 1.0f;
+  float* p = params[t] + s0;
+  const float* g = grads[t] + s0;
+  for (int i = threadIdx.x * 4; i < n; i += 1024) {
+    if (i + 3 < n) {
+      f32x4_t pv = *reinterpret_cast<f32x4_t*>(p + i);
+      const f32x4_t gv = *reinterpret_cast<const f32x4_t*>(g + i);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) pv[r] = pv[r] - lr * (gv[r] * coef);
+      *reinterpret_cast<f32x4_t*>(p + i) = pv;
+    } else {
+      for (int j = i; j < n; ++j) p[j] = p[j] - lr * (g[j] * coef);
+    }
+  }
+}
+
 // Adam family of the trained encoder's group (torch.optim.AdamW, and the reference's BertAdam, Models/Bert/optimization.py:129-152), one
 // form for both:  m = b1 m + (1 - b1) g';  v = b2 v + (1 - b2) g'^2;  p = p dec - a m / (sqrt(v) c + eps).  What differs between the rules,
 // the tensors (decay or none, own step count) and the steps (schedule) is the host's: tab[3 t] = {a, dec, c}.
@@ -148,6 +213,27 @@ extern "C" int ruart_adamax_step(float* const* params, const float* const* grads
   if (n_chunks <= 0 || !clr || !params || !grads || !exp_avg || !exp_inf) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(adamax_update_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg, exp_inf, c_tensor,
                      c_start, c_count, norm_coef, clr, 1.0f - beta1, beta2, eps);
+  RUART_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int ruart_adamax_l2_step(float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_inf,
+                                    const int* c_tensor, const int* c_start, const int* c_count, int n_chunks, const float* norm_coef,
+                                    const float* clr, float beta1, float beta2, float eps, float weight_decay, void* stream) {
+  RUART_ENTRY();
+  if (n_chunks <= 0 || !clr || !params || !grads || !exp_avg || !exp_inf || !c_tensor || !c_start || !c_count) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(adamax_l2_update_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg, exp_inf, c_tensor,
+                     c_start, c_count, norm_coef, clr, 1.0f - beta1, beta2, eps, weight_decay);
+  RUART_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int ruart_sgd_step(float* const* params, const float* const* grads, const int* c_tensor, const int* c_start, const int* c_count,
+                              int n_chunks, const float* norm_coef, float lr, void* stream) {
+  RUART_ENTRY();
+  if (n_chunks <= 0 || !params || !grads || !c_tensor || !c_start || !c_count) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(sgd_update_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, params, grads, c_tensor, c_start, c_count,
+                     norm_coef, lr);
   RUART_CHECK_LAUNCH();
   return 0;
 }

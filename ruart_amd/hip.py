@@ -166,6 +166,8 @@ _SIGNATURES = {
     "ruart_grad_norm_clip": (_I, [_P, _P, _P, _P, _I, _F, _P, _P, _P, _P]),
     "ruart_adamax_step": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _F, _F, _F, _P]),
     "ruart_adam_step": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _F, _F, _F, _P]),
+    "ruart_adamax_l2_step": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _F, _F, _F, _F, _P]),
+    "ruart_sgd_step": (_I, [_P, _P, _P, _P, _P, _I, _P, _F, _P]),
     "ruart_embedding_bwd_sorted": (_I, [_P, _P, _P, _P, _I, _I, _P, _P]),
     "ruart_embedding_bwd_split": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _P, _P, _P]),
     "ruart_phoc_table": (_I, [_P, _P, _I, _P, _I, _P, _P]),

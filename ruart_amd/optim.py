@@ -7,6 +7,10 @@ embedding Parameter to the number of leading rows that are really trained; the r
 their fixed values after every step (:369-373) - are left out of the update (their gradients still enter the clipping norm,
 exactly as in the reference).
 
+The reference's other three ``optimizer`` values step the same way, from one shared base (``_FusedGroup``): ``FusedAdamax(weight_decay=0.5)``
+is 'ADAM' (Adamax with coupled L2 decay, ``ruart_adamax_l2_step``), ``FusedAdam`` is 'ADAM2' (torch.optim.Adam, ``ruart_adam_step``),
+``FusedSGD`` is 'SGD' (``ruart_sgd_step``).  ``select_optimizer`` names the class the trainer builds for a conf.
+
 ``FusedAdamaxAdam`` / ``AdamaxAdam`` (further down): the same step with a trained encoder as an Adam-family group of its own -
 opt['bert_optimizer']."""
 import copy
@@ -19,17 +23,24 @@ from . import hip
 _CHUNK = 8192
 
 
-class FusedAdamax:
-    def __init__(self, params, lr=2e-3, betas=(0.9, 0.999), eps=1e-8, pinned=None):
+class _FusedGroup:
+    """What the fused optimizers over ONE parameter group share - everything but the update rule: the chunk plan, the two staging
+    buffers, the per-step table of gradient pointers and coefficients, ``pinned``, ``extra_sq``, ``norm_coef``, the torch.optim surface
+    and the version bumps.  A rule names its state tensors (``_STATE``, in the order of its kernel's tables), the number of fp32
+    coefficients it sends per tensor and step (``_NCOEF``), and supplies ``_coefficients`` and ``_launch``."""
+    _STATE = ()
+    _NCOEF = 0
+
+    def __init__(self, params, group, pinned=None):
         self.params = [p for p in params]
         for p in self.params:
             if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
-                raise ValueError("FusedAdamax: contiguous fp32 device parameters only")
-        self.param_groups = [{"params": self.params, "lr": lr, "betas": betas, "eps": eps, "weight_decay": 0}]
+                raise ValueError("%s: contiguous fp32 device parameters only" % type(self).__name__)
+        self.param_groups = [dict({"params": self.params}, **group)]
         self.pinned = {id(p): int(n) for p, n in (pinned or {}).items()}
-        self.state = {id(p): {"exp_avg": torch.zeros_like(p), "exp_inf": torch.zeros_like(p)} for p in self.params}
+        self.state = {id(p): {k: torch.zeros_like(p) for k in self._STATE} for p in self.params}
         self.step_count = 0
-        self.steps = {id(p): 0 for p in self.params}      # torch.optim.Adamax counts every parameter's own steps
+        self.steps = {id(p): 0 for p in self.params}      # torch.optim counts every parameter's own steps
         self._plan_key = None
         self.norm_coef = None             # device tensor [total_norm, clip_coef] of the last clip_and_step
 
@@ -53,7 +64,7 @@ class FusedAdamax:
         for g, s in zip(self.param_groups, sd["param_groups"]):
             g.update(s)
         for p, st in zip(self.params, sd["state"]):
-            for k in ("exp_avg", "exp_inf"):
+            for k in self._STATE:
                 self.state[id(p)][k].copy_(st[k])
 
     # -- the step -----------------------------------------------------------------------------------------------------
@@ -72,16 +83,18 @@ class FusedAdamax:
                 tu.append(t); su.append(s); cu.append(min(_CHUNK, n_upd - s))
         ints = torch.tensor(np.concatenate([tn, sn, cn, tu, su, cu]).astype(np.int32), device=dev)
         a, b = len(tn), len(tu)
-        ptrs = torch.tensor([[p.data_ptr() for p in live], [self.state[id(p)]["exp_avg"].data_ptr() for p in live],
-                             [self.state[id(p)]["exp_inf"].data_ptr() for p in live]], dtype=torch.int64, device=dev)
+        ptrs = torch.tensor([[p.data_ptr() for p in live]] + [[self.state[id(p)][k].data_ptr() for p in live] for k in self._STATE],
+                            dtype=torch.int64, device=dev)
+        n_slots = len(live) + (self._NCOEF * len(live) + 1) // 2
         self._plan_val = {"norm": (ints[0:a], ints[a:2 * a], ints[2 * a:3 * a], a),
                           "upd": (ints[3 * a:3 * a + b], ints[3 * a + b:3 * a + 2 * b], ints[3 * a + 2 * b:], b),
                           "ints": ints, "ptrs": ptrs, "partial": torch.empty(a, dtype=torch.float32, device=dev),
                           # gradient tensors are new every step: their pointer table is re-sent (two pinned staging buffers in
                           # turn, so the one of the previous step may still be in flight)
-                          # per step and tensor: gradient pointer (int64) and lr / (1 - beta1^step) (fp32 bits in an int64 slot)
-                          "gptr_host": [torch.empty(2 * len(live), dtype=torch.int64).pin_memory() for _ in range(2)],
-                          "gptr": torch.empty(2 * len(live), dtype=torch.int64, device=dev)}
+                          # per step and tensor: gradient pointer (int64), behind them the rule's fp32 coefficients (_NCOEF per tensor,
+                          # two to an int64 slot)
+                          "gptr_host": [torch.empty(n_slots, dtype=torch.int64).pin_memory() for _ in range(2)],
+                          "gptr": torch.empty(n_slots, dtype=torch.int64, device=dev)}
         self._plan_val["gptr_np"] = [h.numpy() for h in self._plan_val["gptr_host"]]
         self.norm_coef = torch.zeros(2, dtype=torch.float32, device=dev)
 
@@ -101,16 +114,21 @@ class FusedAdamax:
         tab = pl["gptr_np"][slot]
         g0 = self.param_groups[0]
         n_live = len(live)
-        clr = tab[n_live:].view(np.float32)            # first n_live float32 slots of the second half
+        nc = self._NCOEF
+        tab_f = tab[n_live:].view(np.float32) if nc else None      # the rule's coefficients, nc fp32 per tensor
         for i, p in enumerate(live):
             g = p.grad
             if not (g.is_contiguous() and g.dtype == torch.float32):
                 g = p.grad = g.contiguous().float()
             tab[i] = g.data_ptr()
             self.steps[id(p)] += 1
-            clr[i] = g0["lr"] / (1.0 - g0["betas"][0] ** self.steps[id(p)])
+            if nc:
+                j = nc * i
+                for c in self._coefficients(g0, self.steps[id(p)]):
+                    tab_f[j] = c
+                    j += 1
         pl["gptr"].copy_(pl["gptr_host"][slot], non_blocking=True)
-        clr_dev = pl["gptr"][n_live:].view(torch.float32)
+        tab_dev = pl["gptr"][n_live:].view(torch.float32) if nc else None
         lib = hip.kernels()
         st = hip.stream_ptr()
         self.step_count += 1
@@ -119,10 +137,7 @@ class FusedAdamax:
             ct, cs, cc, n = pl["norm"] if extra_sq is None else pl["upd"]
             lib.ruart_grad_norm_clip(pl["gptr"], ct, cs, cc, n, float(max_norm), pl["partial"], self.norm_coef, extra_sq, st)
             coef = self.norm_coef
-        ct, cs, cc, n = pl["upd"]
-        ptrs = pl["ptrs"]
-        lib.ruart_adamax_step(ptrs[0], pl["gptr"], ptrs[1], ptrs[2], ct, cs, cc, n, coef, clr_dev, float(g0["betas"][0]),
-                              float(g0["betas"][1]), float(g0["eps"]), st)
+        self._launch(lib, g0, pl["ptrs"], pl["gptr"], pl["upd"], coef, tab_dev, st)
         # the kernel wrote the parameters through raw pointers: tell torch (version counters feed autograd's saved-tensor checks and
         # the trainable encoder's operand cache, bert_train16.accurate_weights)
         bump = getattr(torch.autograd.graph, "increment_version", None)
@@ -134,6 +149,81 @@ class FusedAdamax:
 
     def step(self):
         self.clip_and_step(None)
+
+
+class FusedAdamax(_FusedGroup):
+    """torch.optim.Adamax, the '#' optimizer; with ``weight_decay`` > 0 the coupled L2 form of the 'ADAM' conf
+    (torch.optim.Adamax(weight_decay=) behind clip_grad_norm_: the decay enters the gradient after the clip).  Without decay the
+    launch is ``ruart_adamax_step``, unchanged."""
+    _STATE = ("exp_avg", "exp_inf")
+    _NCOEF = 1
+
+    def __init__(self, params, lr=2e-3, betas=(0.9, 0.999), eps=1e-8, pinned=None, weight_decay=0):
+        if weight_decay < 0:
+            raise ValueError("FusedAdamax: weight_decay %r is negative" % (weight_decay,))
+        super().__init__(params, {"lr": lr, "betas": betas, "eps": eps, "weight_decay": weight_decay}, pinned)
+
+    @staticmethod
+    def _coefficients(g0, k):
+        return (g0["lr"] / (1.0 - g0["betas"][0] ** k),)      # lr / (1 - beta1^step)
+
+    @staticmethod
+    def _launch(lib, g0, ptrs, gptr, upd, coef, tab, st):
+        ct, cs, cc, n = upd
+        b1, b2, eps, wd = float(g0["betas"][0]), float(g0["betas"][1]), float(g0["eps"]), float(g0["weight_decay"])
+        if wd == 0.0:
+            lib.ruart_adamax_step(ptrs[0], gptr, ptrs[1], ptrs[2], ct, cs, cc, n, coef, tab, b1, b2, eps, st)
+        else:
+            lib.ruart_adamax_l2_step(ptrs[0], gptr, ptrs[1], ptrs[2], ct, cs, cc, n, coef, tab, b1, b2, eps, wd, st)
+
+
+class FusedAdam(_FusedGroup):
+    """torch.optim.Adam without weight decay (the 'ADAM2' conf) on ``ruart_adam_step``: per step and tensor the host sends
+    {a = lr / (1 - beta1^k), dec = 1, c = 1 / sqrt(1 - beta2^k)}, k the tensor's own step count."""
+    _STATE = ("exp_avg", "exp_avg_sq")
+    _NCOEF = 3
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, pinned=None):
+        super().__init__(params, {"lr": lr, "betas": betas, "eps": eps, "weight_decay": 0}, pinned)
+
+    @staticmethod
+    def _coefficients(g0, k):
+        return adam_coefficients("adamw", g0["lr"], 0.0, g0["betas"], k)
+
+    @staticmethod
+    def _launch(lib, g0, ptrs, gptr, upd, coef, tab, st):
+        ct, cs, cc, n = upd
+        lib.ruart_adam_step(ptrs[0], gptr, ptrs[1], ptrs[2], ct, cs, cc, n, coef, tab, float(g0["betas"][0]), float(g0["betas"][1]),
+                            float(g0["eps"]), st)
+
+
+class FusedSGD(_FusedGroup):
+    """torch.optim.SGD without momentum or decay (the 'SGD' conf) on ``ruart_sgd_step``; no state tensors."""
+
+    def __init__(self, params, lr, pinned=None):
+        super().__init__(params, {"lr": lr, "weight_decay": 0}, pinned)
+
+    @staticmethod
+    def _launch(lib, g0, ptrs, gptr, upd, coef, tab, st):
+        ct, cs, cc, n = upd
+        lib.ruart_sgd_step(ptrs[0], gptr, ct, cs, cc, n, coef, float(g0["lr"]), st)
+
+
+_TORCH_NAME = {"#": "Adamax", "ADAM": "Adamax", "ADAM2": "Adam", "SGD": "SGD"}
+_FUSED_NAME = {"#": "FusedAdamax", "ADAM": "FusedAdamax", "ADAM2": "FusedAdam", "SGD": "FusedSGD"}
+
+
+def select_optimizer(opt, device_type):
+    """Name of the class ``SDNetTrainer.setup_model`` builds for ``opt['optimizer']`` on a device of ``device_type``.  The fused
+    classes need a CUDA device.  '#' takes them unless opt['ruart_fused_optimizer'] is false (and, with opt['bert_optimizer'], the
+    two-group forms); 'ADAM', 'ADAM2' and 'SGD' take them only when the key is PRESENT and true - without it they stay on torch.optim."""
+    o = opt["optimizer"]
+    if o not in _TORCH_NAME:
+        raise ValueError("optimizer is wrong")
+    fused = device_type == "cuda" and bool(opt.get("ruart_fused_optimizer", o == "#"))
+    if o == "#" and "bert_optimizer" in opt:
+        return "FusedAdamaxAdam" if fused else "AdamaxAdam"
+    return (_FUSED_NAME if fused else _TORCH_NAME)[o]
 
 
 # -- the trained encoder as a parameter group of its own (opt['bert_optimizer']) ------------------------------------------------

@@ -173,7 +173,7 @@ def read(filename):
 
 def check(ckpt, optimizer, named_tensors, trainable, world=1):
     """Refuse (ValueError naming the mismatch) a state that does not fit the run it is loaded into: format version, world size,
-    optimizer class / rule, a trainable tensor missing from the file, a tensor of another shape.  ``named_tensors``: name -> tensor of
+    optimizer class / rule / weight decay of the first group, a trainable tensor missing from the file, a tensor of another shape.  ``named_tensors``: name -> tensor of
     the live network (parameters and buffers); ``trainable``: the names with requires_grad."""
     ruart = ckpt.get("ruart")
     if not isinstance(ruart, dict) or ruart.get("version") != FORMAT_VERSION:
@@ -187,6 +187,13 @@ def check(ckpt, optimizer, named_tensors, trainable, world=1):
         raise ValueError("train state: optimizer class %s in the file, this run steps with %s" % (ruart["optimizer_class"], cls))
     if ruart["optimizer_rule"] != rule:
         raise ValueError("train state: encoder group rule %r in the file, this run's is %r" % (ruart["optimizer_rule"], rule))
+    # '#' and 'ADAM' step with one class (FusedAdamax, torch.optim.Adamax) and differ in the decay alone, which load_state_dict would overwrite
+    saved = ckpt["state_dict"].get("optimizer")
+    mine, theirs = getattr(optimizer, "param_groups", None) or [], (saved.get("param_groups") if isinstance(saved, dict) else None) or []
+    if mine and theirs and isinstance(mine[0], dict) and isinstance(theirs[0], dict):
+        wd, wd_file = float(mine[0].get("weight_decay", 0)), float(theirs[0].get("weight_decay", 0))
+        if wd != wd_file:
+            raise ValueError("train state: weight decay %g in the file, this run's optimizer has %g" % (wd_file, wd))
     net = ckpt["state_dict"]["network"]
     for n in trainable:
         if n not in net:

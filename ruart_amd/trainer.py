@@ -354,17 +354,24 @@ class SDNetTrainer(BaseTrainer):
             if hasattr(self.network, name):
                 setattr(self.network, name, getattr(self.network, name).to(self.device))
         params = [p for p in self.network.parameters() if p.requires_grad]
+        from .optim import select_optimizer
         o = self.opt["optimizer"]
+        # '#' steps fused unless opt['ruart_fused_optimizer'] is false; 'ADAM', 'ADAM2' and 'SGD' only with the key present and true
+        kind = select_optimizer(self.opt, self.device.type)
+        fused = kind.startswith("Fused")
+        pinned = {}
+        if "TUNE_PARTIAL" in self.opt and (fused or bert_group is not None):
+            # rows >= tune_partial are re-pinned after every step: the fused optimizers never update them
+            for flag, name in (("FastText", "fast_embed"), ("GLOVE", "glove_embed")):
+                if flag in self.opt and getattr(self.network, name).weight.requires_grad:
+                    pinned[getattr(self.network, name).weight] = self.opt["tune_partial"]
         if o == "ADAM":
-            self.optimizer = optim.Adamax(params, weight_decay=0.5, lr=1e-3)
+            if fused:
+                from .optim import FusedAdamax
+                self.optimizer = FusedAdamax(params, lr=1e-3, weight_decay=0.5, pinned=pinned)
+            else:
+                self.optimizer = optim.Adamax(params, weight_decay=0.5, lr=1e-3)
         elif o == "#":
-            fused = self.device.type == "cuda" and self.opt.get("ruart_fused_optimizer", True)
-            pinned = {}
-            if "TUNE_PARTIAL" in self.opt and (fused or bert_group is not None):
-                # rows >= tune_partial are re-pinned after every step: the fused optimizers never update them
-                for flag, name in (("FastText", "fast_embed"), ("GLOVE", "glove_embed")):
-                    if flag in self.opt and getattr(self.network, name).weight.requires_grad:
-                        pinned[getattr(self.network, name).weight] = self.opt["tune_partial"]
             if bert_group is not None:
                 # opt['bert_optimizer']: the trained encoder steps as an Adam-family group of its own, the rest stays under Adamax
                 from .optim import AdamaxAdam, FusedAdamaxAdam, split_parameters
@@ -377,11 +384,17 @@ class SDNetTrainer(BaseTrainer):
             else:
                 self.optimizer = optim.Adamax(params, lr=self.opt.get("lr", 2e-3))
         elif o == "ADAM2":
-            self.optimizer = optim.Adam(params, lr=self.opt.get("lr", 1e-3))
-        elif o == "SGD":
-            self.optimizer = optim.SGD(params, lr=self.opt["lr"])
-        else:
-            raise ValueError("optimizer is wrong")
+            if fused:
+                from .optim import FusedAdam
+                self.optimizer = FusedAdam(params, lr=self.opt.get("lr", 1e-3), pinned=pinned)
+            else:
+                self.optimizer = optim.Adam(params, lr=self.opt.get("lr", 1e-3))
+        else:                # 'SGD' (select_optimizer has refused anything else)
+            if fused:
+                from .optim import FusedSGD
+                self.optimizer = FusedSGD(params, lr=self.opt["lr"], pinned=pinned)
+            else:
+                self.optimizer = optim.SGD(params, lr=self.opt["lr"])
         if self.opt["loss"] in ("BCE", "BCE_D1"):
             self.loss_func = self.instance_bce_with_logits
         elif self.opt["loss"] == "CE":
@@ -566,7 +579,7 @@ class SDNetTrainer(BaseTrainer):
         loss.backward()
         if self.grad_sync is not None:
             self.grad_sync.average_gradients()
-        if hasattr(self.optimizer, "clip_and_step"):       # fused: global-norm clip + Adamax in three launches
+        if hasattr(self.optimizer, "clip_and_step"):       # fused: global-norm clip + the conf's update rule in three launches
             self.optimizer.clip_and_step(self.opt["grad_clipping"],
                                          extra_sq=self.grad_sync.pinned_sq if self.grad_sync is not None else None)
         else:
