@@ -259,7 +259,12 @@ __global__ __launch_bounds__(256, 2) void attn_train_bwd_kernel(const f16_t* __r
     for (int r = 0; r < 4; ++r) {
       const float D = p_drop > 0.f ? drop_scale(sd, attn_drop_idx(tq, q0 + it * 16 + g * 4 + r, lo), p_drop, keep_inv) : 1.0f;
       pd[it][r] = s[it][r] * D;
-      dp[it][r] *= D;                                        // dP = D o dPd
+      {
+        // dP = D o dPd, ROUNDED: fused into dP - delta below, the product would enter unrounded while delta holds the rounded
+        // one, and a one-token sequence (P = 1, delta = dP) would get the rounding residual instead of dS = 0
+#pragma clang fp contract(off)
+        dp[it][r] *= D;
+      }
       delta += s[it][r] * dp[it][r];
     }
   delta += __shfl_xor(delta, 16, 64);
