@@ -421,6 +421,16 @@ int ruart_attn_fwd_pscale(const float* pa, const float* pk, const float* v, cons
 int ruart_attn_bwd_pscale(const float* pa, const float* pk, const float* v, const float* probs, const float* grad_out, const float* diag,
                           int diag_len, int relu, const float* prob_scale, float* grad_pa, float* grad_pk, float* grad_v,
                           float* grad_diag_partial, float* ds_ws, int B, int L1, int L2, int h, int D3, void* stream);
+/* The same operation for 385 <= L2 <= 1024 keys - up to 1024 OCR items / objects: the four entry points above (csrc/sdnet_attention.hip)
+ * serve L2 <= 384, this pair (csrc/sdnet_attention_wide.hip) walks the key / value panels through LDS in blocks of 256 rows and takes
+ * the softmax once over the complete row.  Argument lists, saved pre-dropout `probs`, exact zeros on masked keys, NaN and the NaN flag
+ * for a sample without live keys, grad_diag_partial per 16-query tile: as ruart_attn_fwd_pscale / _bwd_pscale.  hipErrorInvalidValue
+ * before any launch for L2 < 385, L2 > 1024, diag_len outside {0, 1, h} or a non-positive dimension. */
+int ruart_attn_fwd_wide(const float* pa, const float* pk, const float* v, const unsigned char* mask, const float* diag, int diag_len,
+                        int relu, const float* prob_scale, float* out, float* probs, int B, int L1, int L2, int h, int D3, void* stream);
+int ruart_attn_bwd_wide(const float* pa, const float* pk, const float* v, const float* probs, const float* grad_out, const float* diag,
+                        int diag_len, int relu, const float* prob_scale, float* grad_pa, float* grad_pk, float* grad_v,
+                        float* grad_diag_partial, float* ds_ws, int B, int L1, int L2, int h, int D3, void* stream);
 
 /* Layers.py:167-168: F.layer_norm over the WHOLE tensor of n elements, no affine.  stats[0] = mean, stats[1] = rstd.
  * ws: 2 * 1024 floats of scratch. */

@@ -57,6 +57,10 @@ nan_flag = _NanFlag()
 
 
 # ---------------------------------------------------------------------------------------------------------
+ATTN_PANEL_MAX_L2 = 384           # key sets up to here: the whole-panel kernels (csrc/sdnet_attention.hip); above, up to 1024: the
+                                  # key-block kernels (csrc/sdnet_attention_wide.hip).  Each entry point refuses the other's range.
+
+
 class _FusedAttention(torch.autograd.Function):
     """out = softmax_j(mask(a . k^T)) . v with a = act(pa) * diag, k = act(pk)   (Models/Layers.py:228-231, 244, 275-288)."""
 
@@ -71,7 +75,8 @@ class _FusedAttention(torch.autograd.Function):
         dl = 0 if diag is None else diag.numel()
         out = torch.empty(B, L1, D3, dtype=torch.float32, device=pa.device)
         probs = torch.empty(B, L1, L2, dtype=torch.float32, device=pa.device)
-        lib.ruart_attn_fwd_pscale(pa, pk, v, mask, diag, dl, int(relu), pscale, out, probs, B, L1, L2, h, D3, hip.stream_ptr())
+        fwd = lib.ruart_attn_fwd_wide if L2 > ATTN_PANEL_MAX_L2 else lib.ruart_attn_fwd_pscale
+        fwd(pa, pk, v, mask, diag, dl, int(relu), pscale, out, probs, B, L1, L2, h, D3, hip.stream_ptr())
         ctx.save_for_backward(pa, pk, v, probs, diag, pscale)
         ctx.relu = int(relu)
         return out
@@ -96,8 +101,8 @@ class _FusedAttention(torch.autograd.Function):
             kdiag, dl = diag.reshape(1).expand(h).contiguous(), h
         gdiag = (torch.empty(B * ((L1 + 15) // 16), h, dtype=torch.float32, device=pa.device)
                  if (dl > 1 and ctx.needs_input_grad[4]) else None)
-        lib.ruart_attn_bwd_pscale(pa, pk, v, probs, gout, kdiag, dl, ctx.relu, pscale, ga, gk, gv, gdiag, ds, B, L1, L2, h, D3,
-                                  hip.stream_ptr())
+        bwd = lib.ruart_attn_bwd_wide if L2 > ATTN_PANEL_MAX_L2 else lib.ruart_attn_bwd_pscale
+        bwd(pa, pk, v, probs, gout, kdiag, dl, ctx.relu, pscale, ga, gk, gv, gdiag, ds, B, L1, L2, h, D3, hip.stream_ptr())
         if gdiag is None:
             return ga, gk, gv, None, None, None, None
         gd = colsum(gdiag)
@@ -107,7 +112,9 @@ class _FusedAttention(torch.autograd.Function):
 def fused_attention(a, k, v, mask, diag=None, relu=False, prob_scale=None):
     """a (B,L1,h), k (B,L2,h), v (B,L2,D3) fp32; mask (B,L2) uint8/bool (0 = masked key).  With ``relu`` / ``diag`` the
     activation of the reference's AttentionScore is applied inside the kernel: a <- ReLU(a) * diag, k <- ReLU(k).
-    ``prob_scale`` (B,L1,L2) fp32 of 0 / 1/(1-p): dropout on the attention probabilities (BERT)."""
+    ``prob_scale`` (B,L1,L2) fp32 of 0 / 1/(1-p): dropout on the attention probabilities (BERT).
+    1 <= L2 <= 1024: up to 384 keys run ruart_attn_fwd_pscale / _bwd_pscale, 385 .. 1024 ruart_attn_fwd_wide / _bwd_wide; more keys
+    raise ``HipError``."""
     m = mask.to(torch.uint8).contiguous()
     d = None if diag is None else diag.contiguous().view(-1)
     ps = None if prob_scale is None else prob_scale.contiguous()

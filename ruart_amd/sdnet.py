@@ -23,6 +23,9 @@ matrix, so its state at an item's last word is a run over the item's pad positio
 multi2one is 600 wide) and region image features in the one way the
 reference can run them: ``img_feature`` with ``img_fea_way replace_od``, laid under the object items (the overlay form) or, with
 ``img_feature_replace_od``, in their place (the pure form, whose encoder stream carries no object items; batch.img_feature_form).
+Sizes: up to 1024 OCR items / objects (``max_ocr_num``, ``max_od_num``).  The trunk attention takes the items as its keys: up to 384 keys
+run the whole-panel kernels of csrc/sdnet_attention.hip, 385 .. 1024 the key-block kernels of csrc/sdnet_attention_wide.hip
+(ops.fused_attention chooses); the answer scorer takes 1024 slots, the LSTMs and the whole-tensor LayerNorm any length.
 Refused with NotImplementedError: ``img_fea_way final_att`` (the reference builds ``get_answer`` for 3 * ques_final_size and hands it
 ques_final_size: it cannot run), ``fixed_answers`` (its ``fixed_ocr_alpha`` exists under ``final_att`` only), ``multi2one_bidir`` WITH the
 deep attention (its levels project the 1100-wide item rows and the 800-wide question rows with one matrix, Models/Layers.py:227: it
